@@ -1,9 +1,15 @@
 #!/usr/bin/env python
 """bench.py — fv3net ML-physics hot path on MI355X (driver contract).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: set up, settle + W warmup steps, the K
+timed steps, the outputs of the last step to DIR/<name>.npy when --dump-outputs is given
+(same arguments -> same seeded inputs, so two builds compare output for output), and the
+result line.  Everything else (cpu_baseline, extra, extra_scaling below) runs only with
+--full.
 
 A "step" is one pass of the hot path over one batch: BASELINE config #2, the
 column-wise DenseModel predict (fv3fit PureKerasModel.predict -> Keras predict,
@@ -19,8 +25,8 @@ Rank 0 prints ONE JSON line on stdout (everything else goes to stderr), with
                 from the committed rocprofv3 PMC pass (profiles/), or null;
   cpu_baseline: the numpy restatement of the same graph (oracle/dense.py) on the
                 host cores, Keras-style batch_size=32 chunks (pure_keras.py:112 calls
-                model.predict without batch_size), on a bounded sample (N=1, rank 0);
-  extra:        other configs measured on the same GPU (N=1, rank 0).
+                model.predict without batch_size), on a bounded sample (--full, N=1, rank 0);
+  extra:        other configs measured on the same GPU (--full, N=1, rank 0).
 """
 import argparse
 import datetime
@@ -53,8 +59,12 @@ def parse():
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=20)
     p.add_argument("--res", type=int, default=48, help="cubed-sphere resolution per GPU (C48)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-extra", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline does not need: the CPU baseline and the extra / extra_scaling legs")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--no-extra", action="store_true", help="with --full: skip the extra / extra_scaling legs")
     p.add_argument("--cpu-seconds", type=float, default=10.0)
     p.add_argument("--settle-ms", type=float, default=300.0,
                    help="untimed clock-settle phase before the W warmup steps (see timed_steps)")
@@ -276,6 +286,38 @@ def cpu_baseline(wl, seconds):
                   f"float32 in Keras-default batch_size=32 chunks, {dt:.1f} s; numpy BLAS threads="
                   f"{threads}; single-batch (no Keras chunking) = {single:.3e} columns/s",
     }
+
+
+DUMP_BUDGET = 64 * 10**6  # bytes of all dumped arrays together
+
+
+def dump_outputs(wl, directory, rank=0):
+    """Write what the timed path computed in its last step, the arrays a caller of
+    ``wl.step`` receives (``wl.outputs``: (tile, z, y, x) float32 per output variable),
+    as ``directory/<output variable>.npy`` (rank r > 0: ``<name>_rank<r>.npy``).  An
+    output over its share of DUMP_BUDGET is written as a fixed sample of its columns,
+    (z, sampled columns), the columns drawn once by a seeded generator in index order."""
+    import torch
+
+    os.makedirs(directory, exist_ok=True)
+    torch.cuda.synchronize()
+    share = DUMP_BUDGET // len(wl.outputs)
+    written = {}
+    for name, out in zip(wl.model.config.output_variables, wl.outputs):
+        if out.numel() * out.element_size() > share:
+            nz = out.shape[1]
+            ncol = out.numel() // nz
+            keep = share // (nz * out.element_size())
+            idx = np.sort(np.random.default_rng(20240).choice(ncol, keep, replace=False))
+            cols = out.permute(1, 0, 2, 3).reshape(nz, ncol)
+            out = cols[:, torch.from_numpy(idx).to(out.device)]
+        a = out.cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32)
+        path = os.path.join(directory, name + (f"_rank{rank}" if rank else "") + ".npy")
+        np.save(path, a)
+        written[name] = path
+    return written
 
 
 def max_over_ranks(x, dist, dev):
@@ -999,6 +1041,8 @@ def main():
     args = parse()
     if args.legs_only:
         return legs_only(args)
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     import torch
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1025,6 +1069,9 @@ def main():
         t = torch.tensor([wall], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
+    if args.dump_outputs:
+        for name, path in dump_outputs(wl, args.dump_outputs, rank).items():
+            log("BENCH_DUMP", name, path)
     total_cols = wl.ncol * world * args.steps
     value = total_cols / wall
     flops_launch = wl.ncol * wl.flops_per_column
@@ -1068,7 +1115,7 @@ def main():
         },
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             result["cpu_baseline"] = cpu_baseline(wl, args.cpu_seconds)
         except Exception as e:  # the baseline is a report, never fatal
@@ -1077,7 +1124,7 @@ def main():
     torch.cuda.empty_cache()
     if rank == 0:  # the headline alone, on stderr, before any leg runs
         log("BENCH_HEADLINE", compact_line(result))
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         if world == 1:
             result["extra_scaling"], result["extra"] = run_legs_child(args, args.legs_timeout)
         else:

@@ -1,7 +1,8 @@
 """Generate the committed golden fixtures under tests/golden/ (run in the build
 container, where /root/reference exists; the GPU box only reads the .npz files).
 
-* mappm_golden.npz — outputs of the REFERENCE Fortran mappm (mappm.f90 compiled
+* mappm_golden.partN.npz (read as one mapping by tests/golden_io.py) — outputs of
+  the REFERENCE Fortran mappm (mappm.f90 compiled
   unmodified by oracle/Makefile into oracle/_ref/libmappm_ref.so) on seeded
   synthetic columns, for kord in {1,4,7,9,...,17} x iv in {0,1,-1,2}, plus a full
   C12 79->50 case for kord 1 and 10.
@@ -31,6 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 
 from oracle.mappm import build, reference_available, reference_mappm  # noqa: E402
+from tests.golden_io import save_parts  # noqa: E402
 
 REF_JSON = "/root/reference/external/vcm/tests/_coarsen_restarts_regression_tests/reference"
 
@@ -87,7 +89,7 @@ def make_mappm_golden():
     out["c12_pe1"], out["c12_pe2"], out["c12_q"] = pe1, pe2, q
     for kord in (1, 10):
         out[f"c12_k{kord}_iv1"] = reference_mappm(pe1, q, pe2, 1, kord)
-    np.savez_compressed(os.path.join(HERE, "mappm_golden.npz"), **out)
+    save_parts("mappm_golden", out, HERE)  # mappm_golden.partN.npz, each under 1 MiB
 
 
 def make_coarsen_kat():

@@ -3,13 +3,12 @@ golden vectors (flang build of mappm.f90) and the C oracle.  Bar: bit-exact.
 
 Reference: external/mappm/mappm/mappm.f90:10-126; KATs external/vcm/tests/test_mappm.py.
 """
-import os
-
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, require_variant_kernels, set_variant
+from conftest import require_variant_kernels, set_variant
 from oracle.mappm import oracle_mappm
+from tests.golden_io import load_mappm_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -53,7 +52,7 @@ def test_reference_kats_through_f2py_signature(gpu):
 def test_golden_vectors_bit_exact(gpu):
     from tests.remap_exact import mappm_device
 
-    g = np.load(os.path.join(GOLDEN, "mappm_golden.npz"))
+    g = load_mappm_golden()
     for ci in range(len(g["cases"])):
         pe1, pe2 = g[f"c{ci}_pe1"], g[f"c{ci}_pe2"]
         for kord in g["kords"]:

@@ -10,8 +10,9 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+from conftest import ROOT
 from oracle.mappm import oracle_mappm, reference_available, reference_mappm
+from tests.golden_io import load_mappm_golden
 
 HOST_SRC = os.path.join(ROOT, "tests", "native", "mappm_host.cpp")
 HOST_SO = os.path.join(ROOT, "tests", "_build", "libmappm_host.so")
@@ -44,7 +45,7 @@ def test_oracle_reproduces_reference_kats(kat):
 
 
 def test_oracle_matches_reference_golden_vectors():
-    g = np.load(os.path.join(GOLDEN, "mappm_golden.npz"))
+    g = load_mappm_golden()
     n = 0
     for ci in range(len(g["cases"])):
         pe1, pe2 = g[f"c{ci}_pe1"], g[f"c{ci}_pe2"]
@@ -116,7 +117,7 @@ def _host(lib, pe1, q, pe2, iv, kord, cursor=False):
 
 
 def test_streaming_algorithm_matches_golden(host_lib):
-    g = np.load(os.path.join(GOLDEN, "mappm_golden.npz"))
+    g = load_mappm_golden()
     for ci in range(len(g["cases"])):
         pe1, pe2 = g[f"c{ci}_pe1"], g[f"c{ci}_pe2"]
         for kord in g["kords"]:
@@ -204,7 +205,7 @@ def test_output_driven_cursor_is_bit_identical(host_lib, km, kn):
 
 
 def test_output_driven_cursor_golden(host_lib):
-    g = np.load(os.path.join(GOLDEN, "mappm_golden.npz"))
+    g = load_mappm_golden()
     for ci in range(len(g["cases"])):
         pe1, pe2 = g[f"c{ci}_pe1"], g[f"c{ci}_pe2"]
         for kord in g["kords"]:

@@ -12,15 +12,13 @@ itself does not promise bit reproducibility across platforms for this routine
 kord > 7 (cs_profile) is exact whatever the request: its limiter switches on flags of
 the solved edges, which 1-ulp changes flip (mappm.hip, launch_arith).
 """
-import os
-
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
 from oracle import coarsen as OC
 from oracle import restarts as OR
 from oracle.mappm import oracle_mappm
+from tests.golden_io import load_mappm_golden
 from tests.parity import assert_per_level, per_level_errors
 
 pytestmark = pytest.mark.gpu
@@ -40,7 +38,7 @@ def test_golden_vectors_within_1e6(gpu):
     1e-6 per level (measured 3.4e-7), kord > 7 bit-identical (the exact path)."""
     from fv3net_amd.mappm import mappm_device
 
-    g = np.load(os.path.join(GOLDEN, "mappm_golden.npz"))
+    g = load_mappm_golden()
     worst = 0.0
     for ci in range(len(g["cases"])):
         pe1, pe2 = g[f"c{ci}_pe1"], g[f"c{ci}_pe2"]
@@ -66,7 +64,7 @@ def test_f2py_mirror_is_exact(gpu):
     gives NaN as in test_mappm.py:33-44, and golden vectors come back bit for bit."""
     from fv3net_amd import mappm as M
 
-    g = np.load(os.path.join(GOLDEN, "mappm_golden.npz"))
+    g = load_mappm_golden()
     r = M.mappm(g["c12_pe1"].T, g["c12_q"].T, g["c12_pe2"].T, 1, g["c12_pe1"].shape[1], 1, 1, 0.0)
     assert (r.T.view(np.uint32) == g["c12_k1_iv1"].view(np.uint32)).all()
 

@@ -12,7 +12,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 ARGS=("$@")
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \
-    python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline "${ARGS[@]}" > "$OUT/bench_trace.json" 2> "$OUT/bench_trace.err"
+    python3 bench.py --full --steps 100 --warmup 10 --no-cpu-baseline "${ARGS[@]}" > "$OUT/bench_trace.json" 2> "$OUT/bench_trace.err"
 timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o run -- \
     python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-extra "${ARGS[@]}" > "$OUT/bench_fetch.json" 2> "$OUT/bench_fetch.err"
 timeout -k 10 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o run -- \

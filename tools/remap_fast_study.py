@@ -15,6 +15,7 @@ sys.path.insert(0, ROOT)
 from fv3net_amd import workloads as W  # noqa: E402
 from fv3net_amd.coarsen import coarsen_on_pressure  # noqa: E402
 from fv3net_amd.mappm import mappm_device  # noqa: E402
+from tests.golden_io import load_mappm_golden  # noqa: E402
 
 
 def level_err(got, ref, axis_level=0):
@@ -44,7 +45,7 @@ def timeit(fn, n=10):
 
 def main():
     dev = torch.device("cuda", 0)
-    g = np.load(os.path.join(ROOT, "tests", "golden", "mappm_golden.npz"))
+    g = load_mappm_golden()
     worst = {}
     for ci in range(len(g["cases"])):
         pe1, pe2 = g[f"c{ci}_pe1"], g[f"c{ci}_pe2"]
