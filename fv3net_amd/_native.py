@@ -22,6 +22,7 @@ EXPORTED_SYMBOLS = (
     "fv3_build_kind",
     "fv3_mappm",
     "fv3_mappm_ex",
+    "fv3_mappm_arith",
     "fv3_mappm_multi",
     "fv3_dense_create",
     "fv3_dense_destroy",
@@ -91,7 +92,7 @@ EXPORTED_SYMBOLS = (
     "fv3_minmax_scores",
     "fv3_taper_columns",
 )
-ABI_VERSION = 11
+ABI_VERSION = 12
 # the remap arithmetic of fv3_mappm_ex / _multi and the fused coarsen entries
 ARITH_EXACT = 0  # bit-identical to the reference build (mappm.f90 under flang)
 ARITH_FAST = 1   # north_star's 1e-5 rel contract: reciprocal divisions, FMA, hardware MAX / MIN
@@ -245,6 +246,7 @@ _SIGNATURES = {
     "fv3_build_kind": (ctypes.c_char_p, []),
     "fv3_mappm": (_I, [_P, _P, _P, _P, _I64, _I, _I, _I, _I, _F, _P]),
     "fv3_mappm_ex": (_I, [_P, Layout, _P, Layout, _P, Layout, _P, Layout, _I64, _I, _I, _I, _I, _F, _I, _P]),
+    "fv3_mappm_arith": (_I, [_I, _I, _I]),
     "fv3_mappm_multi": (_I, [_P, Layout, ctypes.POINTER(_P), ctypes.POINTER(Layout), _P, Layout, ctypes.POINTER(_P),
                              ctypes.POINTER(Layout), _I, _I64, _I, _I, _I, _I, _F, _I, _P]),
     "fv3_dense_create": (_I, [ctypes.POINTER(DenseDesc), ctypes.POINTER(_P)]),

@@ -21,6 +21,15 @@ except ImportError:  # pragma: no cover
 TOA_PRESSURE = 300.0  # external/vcm/vcm/calc/thermo/constants.py:17
 
 
+def all_finite(tensors) -> bool:
+    """Whether every value of the device tensors is finite (one reduction per tensor on
+    the device, one flag read back): the entry points that mirror reference functions on
+    data from files (``regrid_vertical``, ``restarts.coarsen_restarts_on_pressure``) use
+    it to keep non-finite inputs off the default arithmetic, whose MAX / MIN drop a NaN."""
+    flags = [torch.isfinite(t).all() for t in tensors if t.numel()]
+    return bool(torch.stack(flags).all().item()) if flags else True
+
+
 def coarsen_on_pressure(delp, area, fields: Mapping[str, object], factor: int, iv: int = 1, kord: int = 1,
                         ptop: float = TOA_PRESSURE, stream=None, coarse_delp_f64: bool = False,
                         exact: bool = False):
@@ -29,8 +38,9 @@ def coarsen_on_pressure(delp, area, fields: Mapping[str, object], factor: int, i
     ``coarse_delp_f64`` and delp is float64: the restart-precision
     weighted_block_average(delp, area) of coarsen_restarts.py:480-486).  Device tensors
     in and out.  ``exact`` selects the remap's arithmetic as in ``mappm_device``
-    (default: the 1e-5 rel contract for finite inputs; True: bit-exact to the reference
-    and oracle/coarsen.py, NaNs included)."""
+    (default: the 1e-5 rel contract for finite inputs, with kord 5 and kord 7 / iv 0 on
+    the reference's arithmetic as there; True: bit-exact to the reference and
+    oracle/coarsen.py, NaNs included)."""
     _device.require_gpu()
     delp64 = (isinstance(delp, np.ndarray) and delp.dtype == np.float64) or (
         torch is not None and isinstance(delp, torch.Tensor) and delp.dtype == torch.float64)
@@ -129,10 +139,14 @@ def regrid_vertical(p_in, f_in, p_out, iv: int = 1, kord: int = 1, z_axis: int =
     """Device regrid_vertical (regridz.py:164-279) on arrays whose vertical axis is
     ``z_axis`` (default last, as the reference transposes to); float32 result with
     the input's axis order.  Raises the reference's ValueErrors.  ``exact`` as in
-    ``mappm_device``."""
+    ``mappm_device``, except that this drop-in for a reference function takes whatever a
+    file holds: the inputs are tested for finiteness on the device, and a NaN or an
+    infinity among them selects the reference's arithmetic (which propagates it by
+    position)."""
     from .mappm import mappm_device
 
     p_in, f_in, p_out = (_device.to_device_f32(a) for a in (p_in, f_in, p_out))
+    exact = exact or not all_finite((p_in, f_in, p_out))
     ax = z_axis % p_in.dim()
     if f_in.shape[ax] != p_in.shape[ax] - 1:
         raise ValueError("f_in must have a vertical dimension one shorter than p_in")

@@ -1148,7 +1148,9 @@ int coarsen_arith(int arith, const DT* delp, const float* area, const float* con
 {
     fv3::clear_error();
     FV3_REQUIRE(arith == FV3_ARITH_EXACT || arith == FV3_ARITH_FAST, "regrid_coarsen: unknown arithmetic %d", arith);
-    auto f = arith == FV3_ARITH_FAST ? fv3::fast::regrid_coarsen_impl<DT> : fv3::exact::regrid_coarsen_impl<DT>;
+    // the default arithmetic where it holds its bound (fast_arith_serves, mappm_core.h)
+    auto f = arith == FV3_ARITH_FAST && fv3::fast_arith_serves(iv, kord) ? fv3::fast::regrid_coarsen_impl<DT>
+                                                                         : fv3::exact::regrid_coarsen_impl<DT>;
     return f(delp, area, fields, out, n_fields, delp_out, delp_out64, ntile, km, ny, nx, factor, iv, kord, ptop_toa,
              stream);
 }
@@ -1160,8 +1162,8 @@ int coarsen_edge_arith(int arith, const DT* delp, const float* spacing, const fl
     fv3::clear_error();
     FV3_REQUIRE(arith == FV3_ARITH_EXACT || arith == FV3_ARITH_FAST, "regrid_coarsen_edge: unknown arithmetic %d",
                 arith);
-    auto f = arith == FV3_ARITH_FAST ? fv3::fast::regrid_coarsen_edge_impl<DT>
-                                     : fv3::exact::regrid_coarsen_edge_impl<DT>;
+    auto f = arith == FV3_ARITH_FAST && fv3::fast_arith_serves(iv, kord) ? fv3::fast::regrid_coarsen_edge_impl<DT>
+                                                                         : fv3::exact::regrid_coarsen_edge_impl<DT>;
     return f(delp, spacing, fields, out, n_fields, ntile, km, ny, nx, factor, edge, iv, kord, ptop_toa, stream);
 }
 }  // namespace

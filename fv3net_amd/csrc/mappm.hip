@@ -904,12 +904,22 @@ namespace {
 // flattens a layer or switches its Huynh constraint on flags (extm, ext5, ext6,
 // mappm.f90:269-288) computed from the solved edges, a discontinuous choice: 1-ulp
 // changes to the edges flip it (tools/remap_fast_study.py, C384 kord 10: 7e-3 per level,
-// 1 % of the values moved).  So kord > 7 always runs the exact arithmetic.
+// 1 % of the values moved).  So kord > 7 always runs the exact arithmetic, and so do the
+// ppm_profile calls whose interior limiter is the discontinuous lmt 2 (kord 5; kord 7
+// with iv 0): fast_arith_serves, mappm_core.h.
+bool use_fast(int arith, int iv, int kord) { return arith == FV3_ARITH_FAST && fv3::fast_arith_serves(iv, kord); }
+
 int launch_arith(const MappmArgs& a, int arith, hipStream_t s)
 {
-    return arith == FV3_ARITH_FAST && a.kord <= 7 ? fv3::fast::launch_mappm(a, s) : fv3::exact::launch_mappm(a, s);
+    return use_fast(arith, a.iv, a.kord) ? fv3::fast::launch_mappm(a, s) : fv3::exact::launch_mappm(a, s);
 }
 }  // namespace
+
+extern "C" int fv3_mappm_arith(int iv, int kord, int arith)
+{
+    if (arith != FV3_ARITH_EXACT && arith != FV3_ARITH_FAST) return -1;
+    return use_fast(arith, iv, kord) ? FV3_ARITH_FAST : FV3_ARITH_EXACT;
+}
 
 extern "C" int fv3_mappm_ex(const float* pe1, fv3_layout pe1_l, const float* q1, fv3_layout q1_l,
                             const float* pe2, fv3_layout pe2_l, float* q2, fv3_layout q2_l,
@@ -969,8 +979,8 @@ extern "C" int fv3_mappm_multi(const float* pe1, fv3_layout pe1_l, const float* 
         for (; f + 2 <= n_fields; f += 2) {
             fv3::MappmPairArgs a{pe1, pe2, pe1_l, pe2_l, {q1[f], q1[f + 1]}, {q2[f], q2[f + 1]},
                                  {q1_l[f], q1_l[f + 1]}, {q2_l[f], q2_l[f + 1]}, ncol, km, kn, iv, kord};
-            const int st = arith == FV3_ARITH_FAST ? fv3::fast::launch_mappm_pairs(a, s)
-                                                   : fv3::exact::launch_mappm_pairs(a, s);
+            const int st = use_fast(arith, iv, kord) ? fv3::fast::launch_mappm_pairs(a, s)
+                                                     : fv3::exact::launch_mappm_pairs(a, s);
             if (st != FV3_OK) return st;
         }
     }

@@ -49,12 +49,39 @@
 //     operand is dropped instead of propagated by position, so non-finite inputs need the
 //     exact path.
 // Same algorithm, same order of operations, same limiter branches (a comparison near its
-// switching point may take the other branch; the PPM limiters are continuous there).
+// switching point may take the other branch; the limiters this policy serves are
+// continuous there).  ppm_limiters lmt 2 is not: its `fmin < 0` test on a parabola whose
+// minimum touches zero (a tracer with exact zeros) replaces the whole parabola, so a
+// 1-ulp change moves the layer by a quarter of its scale.  fast_arith_serves() below
+// keeps the calls that reach it (kord 5; kord 7 with iv 0), like kord > 7, on the
+// reference's arithmetic; the hosts that pick an arithmetic ask it.
+namespace fv3 {
+// The limiter ppm_profile applies to an interior layer (2 < L < km - 1), as the columns
+// below select it (mappm_ppm_column's `lmt` and its Huynh branch; ppm_profile,
+// mappm.f90:614-851): ppm_limit's lmt, 3 standing for "none".
+FV3_HD inline int ppm_interior_lmt(int iv, int kord)
+{
+    if (kord >= 7) return iv == 0 ? 2 : 3;  // Huynh's constraint, then lmt 2 for iv 0 only
+    if (kord == 6) return 3;
+    int lmt = kord - 3;
+    lmt = lmt > 0 ? lmt : 0;
+    if (iv == 0) lmt = lmt < 2 ? lmt : 2;
+    return lmt;
+}
+// Whether the FV3_FAST_ARITH policy may serve a call: the ppm_profile path (kord <= 7;
+// cs_profile switches on flags of its solved edges, mappm.hip) whose interior limiter is
+// not the discontinuous lmt 2.
+FV3_HD inline bool fast_arith_serves(int iv, int kord) { return kord <= 7 && ppm_interior_lmt(iv, kord) != 2; }
+}  // namespace fv3
+
 #ifdef FV3_FAST_ARITH
 #define FV3_ARITH_NS fast
+// A host test build may define FV3_RCP (a reciprocal within 1 ulp, like the device's) and
+// FV3_HOST_DEVICE_DIV (div_refined by the device's formula) before the include, to see the
+// device's rounding on the CPU (tests/native/mappm_host.cpp).
 #if defined(__HIP_DEVICE_COMPILE__)
 #define FV3_RCP(b) __builtin_amdgcn_rcpf(b)
-#else
+#elif !defined(FV3_RCP)
 #define FV3_RCP(b) (1.0f / (b))
 #endif
 namespace fv3 {
@@ -67,7 +94,7 @@ FV3_HD inline float div_refined(float a, float b)
 {
     const float r = FV3_RCP(b);
     const float q = a * r;
-#if defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__) || defined(FV3_HOST_DEVICE_DIV)
     return __builtin_fmaf(__builtin_fmaf(-b, q, a), r, q);
 #else
     return a / b;

@@ -18,6 +18,13 @@ except ImportError:  # pragma: no cover
     torch = None
 
 
+def runs_exact(iv: int = 1, kord: int = 1, exact: bool = False) -> bool:
+    """Whether a remap with (iv, kord) runs the reference's arithmetic when ``exact`` is
+    asked for: always with ``exact=True``, and under the default for the calls the fast
+    arithmetic does not serve (``fast_arith_serves``, csrc/mappm_core.h)."""
+    return _native.load().fv3_mappm_arith(int(iv), int(kord), _native.arith(exact)) == _native.ARITH_EXACT
+
+
 def mappm_device(pe1, q1, pe2, iv: int = 1, kord: int = 1, out=None, stream=None, exact: bool = False):
     """Remap on device.  ``pe1 [km+1, ncol]``, ``q1 [km, ncol]``, ``pe2 [kn+1, ncol]``
     float32 CUDA tensors (column fastest, the Fortran pe1(i,k) order; strided views
@@ -26,8 +33,11 @@ def mappm_device(pe1, q1, pe2, iv: int = 1, kord: int = 1, out=None, stream=None
 
     ``exact=False`` (default): north_star's floating-point contract (within 1e-5 rel of
     the reference; reciprocal divisions, FMA, hardware MAX / MIN, csrc/mappm_core.h) for
-    finite inputs.  ``exact=True``: the reference build's arithmetic, bit for bit, for
-    every input (NaNs included)."""
+    finite inputs.  Calls that arithmetic cannot hold to 1e-5 run the reference's
+    whatever is asked: kord > 7, and the ppm_profile calls whose interior limiter is the
+    discontinuous lmt 2 (kord 5; kord 7 with iv 0; ``fast_arith_serves``,
+    csrc/mappm_core.h).  ``exact=True``: the reference build's arithmetic, bit for bit,
+    for every input (NaNs included)."""
     _device.require_gpu()
     for a in (pe1, q1, pe2):
         if len(getattr(a, "shape", ())) != 2:

@@ -28,7 +28,7 @@ from typing import Dict, Mapping
 import numpy as np
 
 from . import _device, _native
-from .coarsen import TOA_PRESSURE, coarsen_edges_on_pressure, coarsen_on_pressure
+from .coarsen import TOA_PRESSURE, all_finite, coarsen_edges_on_pressure, coarsen_on_pressure
 
 try:
     import torch
@@ -110,7 +110,10 @@ def coarsen_restarts_on_pressure(coarsening_factor: int, grid_spec: Mapping[str,
                                  exact: bool = False) -> Dict[str, Dict[str, object]]:
     """coarsen_restarts_on_pressure (coarsen_restarts.py:152-225) for fv_core.res,
     fv_tracer.res and (if given) fv_srf_wnd.res.  Returns {category: {name: tensor}}.
-    ``exact`` selects the pressure remap's arithmetic (``coarsen.coarsen_on_pressure``)."""
+    ``exact`` selects the pressure remap's arithmetic (``coarsen.coarsen_on_pressure``).
+    The restart data come from files, so delp and the remapped fields are tested for
+    finiteness on the device first: a NaN or an infinity among them selects the
+    reference's arithmetic, which propagates it by position."""
     _device.require_gpu()
     if "sfc_data" in restarts:
         raise NotImplementedError("sfc_data ('complex' surface coarsening) is outside this build's scope; "
@@ -140,14 +143,17 @@ def coarsen_restarts_on_pressure(coarsening_factor: int, grid_spec: Mapping[str,
     fused.update({("t", n): strip(tracer[n]) for n in tracer_names})
     keys = list(fused)
     names = [f"{c}:{n}" for c, n in keys]
+    fused = {k: _device.to_device_f32(v) for k, v in fused.items()}
+    u, v = _device.to_device_f32(strip(core["u"])), _device.to_device_f32(strip(core["v"]))
+    exact = exact or not all_finite([delp, u, v] + list(fused.values()))
     res, delp_c = coarsen_on_pressure(delp, area, dict(zip(names, (fused[k] for k in keys))), f, iv, kord,
                                       stream=stream, coarse_delp_f64=True, exact=exact)
     out_core = {n: res[f"c:{n}"] for n in masked}
     out_tracer = {n: res[f"t:{n}"] for n in tracer_names}
     out_core["delp"] = delp_c
-    out_core["u"] = coarsen_edges_on_pressure(delp, grid_spec["dx"], {"u": strip(core["u"])}, f, "x", iv, kord,
+    out_core["u"] = coarsen_edges_on_pressure(delp, grid_spec["dx"], {"u": u}, f, "x", iv, kord,
                                               stream=stream, exact=exact)["u"]
-    out_core["v"] = coarsen_edges_on_pressure(delp, grid_spec["dy"], {"v": strip(core["v"])}, f, "y", iv, kord,
+    out_core["v"] = coarsen_edges_on_pressure(delp, grid_spec["dy"], {"v": v}, f, "y", iv, kord,
                                               stream=stream, exact=exact)["v"]
     plain = weighted_block_average({"phis": strip(core["phis"]), "DZ": strip(core["DZ"])}, area, f, stream)
     out_core["DZ"], out_core["phis"] = impose_hydrostatic_balance(out_core["T"], out_tracer["sphum"], delp_c,

@@ -61,7 +61,8 @@ int fv3_abi_version(void); /* bumped on any signature change (2: emulator fields
                                  fv3_sum_squares, fv3_cos_zenith,
                               10: fv3_step_partials_f64, fv3_fold_rows_repeat,
                               11: the `arith` argument of fv3_mappm_ex / _multi and of the
-                                  fused coarsen entries) */
+                                  fused coarsen entries,
+                              12: fv3_mappm_arith) */
 const char* fv3_build_kind(void); /* "product" (fv3net_amd/build.py, no experiment knob compiled in)
                                      or "experiment" (a tools/ variant: results may be invalid) */
 
@@ -92,9 +93,15 @@ typedef struct {
  *   FV3_ARITH_FAST   north_star's floating-point contract (1e-5 rel): divisions by
  *                    v_rcp_f32 reciprocals, FMA within an expression, hardware MAX / MIN
  *                    (csrc/mappm_core.h).  Same algorithm and limiter logic; finite
- *                    inputs only (a NaN operand of MAX / MIN is dropped, not propagated). */
+ *                    inputs only (a NaN operand of MAX / MIN is dropped, not propagated).
+ *                    A call this arithmetic cannot hold to 1e-5 runs FV3_ARITH_EXACT
+ *                    whatever is asked: kord > 7 (cs_profile), and the ppm_profile calls
+ *                    whose interior limiter is the discontinuous lmt 2 (kord 5; kord 7
+ *                    with iv 0).  fv3_mappm_arith tells which arithmetic a call runs. */
 #define FV3_ARITH_EXACT 0
 #define FV3_ARITH_FAST 1
+int fv3_mappm_arith(int iv, int kord, int arith); /* the arithmetic a remap with (iv, kord) runs when
+                                                     `arith` is asked for; -1: unknown `arith` */
 int fv3_mappm(const float* pe1, const float* q1, const float* pe2, float* q2, int64_t ncol,
               int km, int kn, int iv, int kord, float ptop, void* stream);
 

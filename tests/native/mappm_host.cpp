@@ -1,8 +1,29 @@
 // TEST-ONLY host build of the product's streaming mappm (fv3net_amd/csrc/mappm_core.h).
 // Lets the CPU test suite check the one-pass algorithm bit-for-bit against the
 // oracle without a GPU.  Not part of the product library and never loaded by it.
+//
+// With -DFV3_FAST_ARITH -DFV3_EMULATE_DEVICE_RCP (and FMA contraction available, -mfma) it
+// is the default arithmetic as the device rounds it: the reciprocal is the correctly
+// rounded one moved by +1 / -1 ulp for a quarter of the denominators each (the device's
+// v_rcp_f32 is good to 1 ulp; a function of the denominator, so equal denominators share
+// one reciprocal as on the device), and div_refined takes the device's FMA refinement.
+#include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <vector>
+#if defined(FV3_FAST_ARITH) && defined(FV3_EMULATE_DEVICE_RCP)
+static inline float fv3_emulated_rcp(float b)
+{
+    const float r = 1.0f / b;
+    uint32_t u;
+    std::memcpy(&u, &b, 4);
+    const uint32_t h = (u * 2654435761u) >> 30;  // 0, 1: as rounded; 2: one ulp up; 3: one ulp down
+    if (h < 2 || !std::isfinite(r) || r == 0.0f) return r;
+    return h == 2 ? std::nextafterf(r, INFINITY) : std::nextafterf(r, -INFINITY);
+}
+#define FV3_RCP(b) fv3_emulated_rcp(b)
+#define FV3_HOST_DEVICE_DIV 1
+#endif
 #include "../../fv3net_amd/csrc/mappm_core.h"
 
 namespace {
@@ -23,6 +44,9 @@ struct Scr {
     float& g(int k) { return gv[k]; }
 };
 }  // namespace
+
+// whether the default arithmetic serves (iv, kord), as the product's hosts ask it
+extern "C" int host_fast_arith_serves(int iv, int kord) { return fv3::fast_arith_serves(iv, kord) ? 1 : 0; }
 
 extern "C" int host_mappm(int km, const float* pe1, const float* q1, int kn, const float* pe2,
                           float* q2, int64_t ncol, int iv, int kord)

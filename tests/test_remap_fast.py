@@ -10,7 +10,11 @@ itself does not promise bit reproducibility across platforms for this routine
 (external/vcm/tests/test_coarsen_restarts.py:115-122 compares with assert_allclose).
 
 kord > 7 (cs_profile) is exact whatever the request: its limiter switches on flags of
-the solved edges, which 1-ulp changes flip (mappm.hip, launch_arith).
+the solved edges, which 1-ulp changes flip (mappm.hip, launch_arith).  So are kord 5 and
+kord 7 with iv 0, whose interior limiter (ppm_limiters lmt 2) is discontinuous where a
+parabola's minimum touches zero (fast_arith_serves, csrc/mappm_core.h;
+tests/test_remap_fast_host.py).  tests/test_remap_default_matrix.py holds the default
+path to the oracle on every kernel the host picks by size.
 """
 import numpy as np
 import pytest
@@ -67,6 +71,8 @@ def test_f2py_mirror_is_exact(gpu):
     g = load_mappm_golden()
     r = M.mappm(g["c12_pe1"].T, g["c12_q"].T, g["c12_pe2"].T, 1, g["c12_pe1"].shape[1], 1, 1, 0.0)
     assert (r.T.view(np.uint32) == g["c12_k1_iv1"].view(np.uint32)).all()
+    kat = [np.asarray(v, np.float32)[None, :] for v in ([1, 2, 3, 2, 5], [np.nan] * 4, [0, 2.5, 3.5, 4.5, 50])]
+    assert np.isnan(np.asarray(M.mappm(*kat, 1, 1, 1, 1, 0.0))).all()
 
 
 @pytest.mark.parametrize("kord", [1, 4, 6, 7])
@@ -91,7 +97,8 @@ def test_random_columns_vs_oracle(gpu, kord, iv):
 def test_c384_grid_vs_exact(gpu, kord):
     """The bench's config #3 columns (C384, 884,736 columns, 79 -> 79): the default
     arithmetic against the exact kernel over the whole grid (kord 1 measured 4.2e-7 per
-    level with no flip; kord 10 runs exact: identical)."""
+    level with no flip, and 3.1e-7 with none on seeds 6, 7 and 8; kord 10 runs exact:
+    identical)."""
     import torch
 
     from fv3net_amd import workloads as W
@@ -103,9 +110,9 @@ def test_c384_grid_vs_exact(gpu, kord):
     rel = (fast.double() - exact.double()).abs() / exact.double().abs().amax(1, keepdim=True)
     if kord > 7:
         assert rel.max().item() == 0.0
-    else:  # flips as in test_coarsen_c384_vs_exact: counted, at most 2 of 69.9 M values
-        assert int((rel > 1e-5).sum()) <= 2 and rel.max().item() <= 1e-3
-        assert 0.0 < rel[rel <= 1e-5].max().item() <= 1e-6
+    else:  # no value of the 69.9 M beyond the contract (no limiter flip)
+        assert rel.max().item() <= 1e-5
+        assert 0.0 < rel.max().item() <= 1e-6
 
 
 def test_pairs_and_split_lanes_vs_single(gpu):
@@ -153,10 +160,11 @@ def test_coarsen_c384_vs_exact(gpu, nfields):
     """Config #3 at full size (C384 -> C48, 1,092,096 coarse values per field): the
     default arithmetic against the exact kernel.  The reference's limiter flattens a
     layer when its dc is exactly 0 (ppm_limiters lmt 0, `dm == 0`); a layer whose dc
-    sits within an ulp of that switch can take the other branch, which moves that one
-    fine value by its curvature term.  Such flips are counted: at most 2 coarse values
-    per field beyond 1e-5 of their level's scale (measured: 0 or 1), none beyond 1e-4,
-    and every other value within 2e-6 (measured 1.6e-6)."""
+    sits within an ulp of that switch could take the other branch, which would move that
+    one fine value by its curvature term.  With the end cubics on the reference's
+    arithmetic in both policies (csrc/mappm_core.h), seeds 5 to 8 with 1 and 4 fields
+    showed no coarse value beyond 1e-5 of its level's scale (worst 4.2e-7): none is
+    allowed, and every value stays within 2e-6."""
     import torch
 
     from fv3net_amd import workloads as W
@@ -168,9 +176,8 @@ def test_coarsen_c384_vs_exact(gpu, nfields):
     for k in fast:
         f, e = fast[k].double(), exact[k].double()
         rel = (f - e).abs() / e.abs().amax((0, 2, 3), keepdim=True)
-        flips = int((rel > 1e-5).sum())
-        assert flips <= 2 and rel.max().item() <= 1e-4, (k, flips, rel.max().item())
-        assert rel[rel <= 1e-5].max().item() <= 2e-6, k
+        assert rel.max().item() <= 1e-5, (k, int((rel > 1e-5).sum()), rel.max().item())
+        assert rel.max().item() <= 2e-6, k
 
 
 @pytest.mark.parametrize("edge", ["x", "y"])
