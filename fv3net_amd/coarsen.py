@@ -42,13 +42,7 @@ def coarsen_on_pressure(delp, area, fields: Mapping[str, object], factor: int, i
     the reference's arithmetic as there; True: bit-exact to the reference and
     oracle/coarsen.py, NaNs included)."""
     _device.require_gpu()
-    delp64 = (isinstance(delp, np.ndarray) and delp.dtype == np.float64) or (
-        torch is not None and isinstance(delp, torch.Tensor) and delp.dtype == torch.float64)
-    if delp64:  # keep restart precision: pressures are cumulated in float64 on device
-        delp = (torch.as_tensor(delp) if not isinstance(delp, torch.Tensor) else delp).to(
-            device=torch.device("cuda", torch.cuda.current_device()), dtype=torch.float64).contiguous()
-    else:
-        delp = _device.to_device_f32(delp)
+    delp, delp64 = _delp_on_device(delp)
     area = _device.to_device_f32(area)
     if delp.dim() != 4 or area.dim() != 3:
         raise ValueError("delp must be (tile, z, y, x) and area (tile, y, x)")

@@ -3,22 +3,31 @@
 // Replaces the f2py-wrapped Fortran mappm (external/mappm/mappm/mappm.f90:10-126)
 // as called by vcm.cubedsphere.regrid_vertical (external/vcm/vcm/cubedsphere/regridz.py:273).
 //
-// One thread per column; the column-fastest [level][column] layout (Fortran's
-// pe1(i,k)) makes every per-level load a coalesced 256 B wave access.  The
-// per-column algorithm is the one-pass streaming formulation in mappm_core.h:
-// kord <= 7 runs entirely in registers (no LDS, no scratch) -- or, below
-// kLevelsMaxCols columns, one block per column with a lane per level; kord > 7 solves
-// cs_profile's tridiagonal edge system into a [2][km+3][column] scratch in global
-// memory (coalesced; LDS kept behind FV3_MAPPM_LDS), then streams.
+// The column-fastest [level][column] layout (Fortran's pe1(i,k)) makes every per-level
+// load a coalesced 256 B wave access.  The per-column algorithm is the one-pass streaming
+// formulation in mappm_core.h / mappm_multi.h.  kord <= 7 (ppm_profile) has four kernels,
+// all with the one-lane kernel's bits; ppm_kernel_choice (mappm_choice.h) picks one from
+// the fields per launch, the column count and the device's CUs:
+//   * mappm_ppm_levels_kernel: one block per column, a lane per level, for grids too small
+//     to fill the chip with columns (one field per launch);
+//   * mappm_ppm_pair_split_kernel<NF, K1, 3> and <NF, K1, 2>: one or two fields with three
+//     or two lanes per column, each streaming a share of the outputs, while all their waves
+//     are resident (the default from 10,240 columns for pairs, 20,480 for one field);
+//   * mappm_ppm_kernel (one field) and mappm_ppm_pair_kernel (two): one lane per column,
+//     entirely in registers (no LDS, no scratch), on the large grids.
+// kord > 7 solves cs_profile's tridiagonal edge system into a [2][km+3][column] scratch in
+// global memory (coalesced; LDS kept behind FV3_MAPPM_LDS), then streams.
 // Roofline: HBM-bound at (km+1 + km + kn+1 + kn) * 4 B per column, with ~150
 // VALU ops per input level (including ~7 IEEE divides) close behind.
 #define FV3_HD __host__ __device__
 #include "common.h"
+#include "mappm_choice.h"
 #include "mappm_core.h"
 #include "mappm_multi.h"
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 namespace fv3 {
 
@@ -46,14 +55,36 @@ struct MappmPairArgs {
     int km, kn, iv, kord;
 };
 
+// CUs of the current device, queried once (thread-safe static initialisation)
+inline int device_cus()
+{
+    static const int n_cu = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+            n = 256;
+        return n;
+    }();
+    return n_cu;
+}
+
+// the kord <= 7 kernel of a launch of `fields` fields on this device (mappm_choice.h); the
+// knobs of the choice are read here and nowhere else
+inline PpmKernel ppm_kernel(int fields, int64_t ncol, int km, int kn)
+{
+    const PpmKnobs knobs{variant_env("FV3_MAPPM_PATH"), variant_env("FV3_MAPPM_SPLIT"),
+                         variant_env("FV3_MAPPM_SPLIT1")};
+    return ppm_kernel_choice(fields, ncol, km, kn, device_cus(), knobs);
+}
+
 namespace FV3_ARITH_NS {
 int launch_mappm(MappmArgs a, hipStream_t stream);
-int launch_mappm_pairs(const MappmPairArgs& a, hipStream_t stream);
+int launch_mappm_pairs(MappmPairArgs a, int lanes, hipStream_t stream);
 }  // namespace FV3_ARITH_NS
 #ifndef FV3_FAST_ARITH
 namespace fast {  // mappm_fast.hip
 int launch_mappm(MappmArgs a, hipStream_t stream);
-int launch_mappm_pairs(const MappmPairArgs& a, hipStream_t stream);
+int launch_mappm_pairs(MappmPairArgs a, int lanes, hipStream_t stream);
 }  // namespace fast
 #endif
 
@@ -67,22 +98,18 @@ namespace {
 #define FV3_MAPPM_EDGE_AHEAD 1  // next_edge's load one call ahead (0: tools A/B builds)
 #endif
 
-struct DevCol {
-    const float* pe1_;
-    const float* q1_;
+struct EdgeCursor {
     const float* pe2_;
-    float* q2_;
-    int64_t ld_pe1, ld_q1, ld_pe2, ld_q2;
+    int64_t ld_pe2;
     int kn;
     const float* pe2_next;  // the edge after nb
     float nb;               // pe2(k + 1) for the next next_edge(k), loaded one call ahead
-    __device__ __forceinline__ float q1(int k) const { return q1_[(int64_t)(k - 1) * ld_q1]; }
-    __device__ __forceinline__ float pe1(int k) const { return pe1_[(int64_t)(k - 1) * ld_pe1]; }
     __device__ __forceinline__ float pe2(int k) const { return pe2_[(int64_t)(k - 1) * ld_pe2]; }
-    __device__ __forceinline__ void emit(int, float v)
+    // the cursor where the single pass has it when it begins output k_first (1: a whole column)
+    __device__ __forceinline__ void seek(int k_first)
     {
-        *q2_ = v;
-        q2_ += ld_q2;
+        pe2_next = pe2_ + (int64_t)(k_first + 1) * ld_pe2;
+        nb = (k_first + 2 <= kn + 1) ? *pe2_next : 0.0f;
     }
     __device__ __forceinline__ float next_edge(int k)
     {
@@ -91,11 +118,28 @@ struct DevCol {
         const float r = nb;
         pe2_next += ld_pe2;
         nb = (k + 2 <= kn + 1) ? *pe2_next : 0.0f;
-#else
+#else  // A/B variant builds: loaded at the call
         const float r = *pe2_next;
         pe2_next += ld_pe2;
 #endif
         return r;
+    }
+};
+
+struct DevCol {
+    const float* pe1_;
+    const float* q1_;
+    float* q2_;
+    int64_t ld_pe1, ld_q1, ld_q2;
+    EdgeCursor edge;
+    __device__ __forceinline__ float pe2(int k) const { return edge.pe2(k); }
+    __device__ __forceinline__ float next_edge(int k) { return edge.next_edge(k); }
+    __device__ __forceinline__ float q1(int k) const { return q1_[(int64_t)(k - 1) * ld_q1]; }
+    __device__ __forceinline__ float pe1(int k) const { return pe1_[(int64_t)(k - 1) * ld_pe1]; }
+    __device__ __forceinline__ void emit(int, float v)
+    {
+        *q2_ = v;
+        q2_ += ld_q2;
     }
 };
 
@@ -119,32 +163,17 @@ struct DevColBuf {
     MRsrc r_pe1, r_q1;
     uint32_t o_pe1, o_q1;     // lane byte offsets
     uint32_t lb_pe1, lb_q1;   // level strides in bytes
-    const float* pe2_;
     float* q2_;
-    int64_t ld_pe2, ld_q2;
-    int kn;
-    const float* pe2_next;  // the edge after nb
-    float nb;               // pe2(k + 1) for the next next_edge(k), loaded one call ahead
+    int64_t ld_q2;
+    EdgeCursor edge;
+    __device__ __forceinline__ float pe2(int k) const { return edge.pe2(k); }
+    __device__ __forceinline__ float next_edge(int k) { return edge.next_edge(k); }
     __device__ __forceinline__ float q1(int k) const { return bload(r_q1, o_q1, (uint32_t)(k - 1) * lb_q1); }
     __device__ __forceinline__ float pe1(int k) const { return bload(r_pe1, o_pe1, (uint32_t)(k - 1) * lb_pe1); }
-    __device__ __forceinline__ float pe2(int k) const { return pe2_[(int64_t)(k - 1) * ld_pe2]; }
     __device__ __forceinline__ void emit(int, float v)
     {
         *q2_ = v;
         q2_ += ld_q2;
-    }
-    __device__ __forceinline__ float next_edge(int k)
-    {
-        if (k + 1 > kn + 1) return 0.0f;
-#if FV3_MAPPM_EDGE_AHEAD
-        const float r = nb;
-        pe2_next += ld_pe2;
-        nb = (k + 2 <= kn + 1) ? *pe2_next : 0.0f;
-#else  // A/B variant builds: loaded at the call
-        const float r = *pe2_next;
-        pe2_next += ld_pe2;
-#endif
-        return r;
     }
 };
 
@@ -193,15 +222,14 @@ __device__ __forceinline__ DevCol make_col(const MappmArgs& a, int64_t c)
     DevCol d;
     d.pe1_ = a.pe1 + col_offset(a.l_pe1, c);
     d.q1_ = a.q1 + col_offset(a.l_q1, c);
-    d.pe2_ = a.pe2 + col_offset(a.l_pe2, c);
+    d.edge.pe2_ = a.pe2 + col_offset(a.l_pe2, c);
     d.q2_ = a.q2 + col_offset(a.l_q2, c);
     d.ld_pe1 = a.l_pe1.ld;
     d.ld_q1 = a.l_q1.ld;
-    d.ld_pe2 = a.l_pe2.ld;
+    d.edge.ld_pe2 = a.l_pe2.ld;
     d.ld_q2 = a.l_q2.ld;
-    d.kn = a.kn;
-    d.pe2_next = d.pe2_ + 2 * d.ld_pe2;
-    d.nb = d.kn >= 2 ? *d.pe2_next : 0.0f;
+    d.edge.kn = a.kn;
+    d.edge.seek(1);
     return d;
 }
 
@@ -216,13 +244,12 @@ __device__ __forceinline__ DevColBuf make_col_buf(const MappmArgs& a, int64_t c)
     d.o_q1 = (uint32_t)(col_offset(a.l_q1, c) * 4);
     d.lb_pe1 = (uint32_t)(a.l_pe1.ld * 4);
     d.lb_q1 = (uint32_t)(a.l_q1.ld * 4);
-    d.pe2_ = a.pe2 + col_offset(a.l_pe2, c);
+    d.edge.pe2_ = a.pe2 + col_offset(a.l_pe2, c);
     d.q2_ = a.q2 + col_offset(a.l_q2, c);
-    d.ld_pe2 = a.l_pe2.ld;
+    d.edge.ld_pe2 = a.l_pe2.ld;
     d.ld_q2 = a.l_q2.ld;
-    d.kn = a.kn;
-    d.pe2_next = d.pe2_ + 2 * d.ld_pe2;
-    d.nb = a.kn >= 2 ? *d.pe2_next : 0.0f;
+    d.edge.kn = a.kn;
+    d.edge.seek(1);
     return d;
 }
 
@@ -272,11 +299,13 @@ __global__ __launch_bounds__(256) FV3_PPM_WPE_ATTR void mappm_ppm_kernel(MappmAr
     }
 }
 
-bool is_k1(int iv, int kord) { return iv == 1 && kord == 1; }
-
-// tools/ab.py, kord 1 79->79: C48 (13,824 columns) 142 -> 38 us, C96
-// (55,296) 168 -> 118 us; at C384 the serial kernel (0.70 ms) wins.
-constexpr int64_t kLevelsMaxCols = 65536;
+// the K1 / general pick of a launch: kernel_of(std::true_type / std::false_type) names the
+// kernel of either build
+template <class F>
+const void* pick_k1(int iv, int kord, F kernel_of)
+{
+    return (iv == 1 && kord == 1) ? kernel_of(std::true_type{}) : kernel_of(std::false_type{});
+}
 
 // No-op edge source for remap_one (the level-parallel kernel finishes one output
 // layer per lane, so the next edge is never read).
@@ -513,27 +542,143 @@ const void* cs_global_kernel(const MappmArgs& a, int64_t nlanes)
 
 }  // namespace
 
+// ---- one or two fields on one column's edges (fv3_mappm_multi, the lane-split kernels) ----
 
+// DevCol for mappm_ppm_columns<NF> (NF = 1, 2): fields f emit output k in turn, so each
+// keeps its own running output pointer
+template <int NF>
+struct DevColN {
+    const float* pe1_;
+    const float* q1_[NF];
+    float* q2_[NF];
+    int64_t ld_pe1, ld_q1[NF], ld_q2[NF];
+    EdgeCursor edge;
+    __device__ __forceinline__ float pe2(int k) const { return edge.pe2(k); }
+    __device__ __forceinline__ float next_edge(int k) { return edge.next_edge(k); }
+    __device__ __forceinline__ float q1(int f, int k) const { return q1_[f][(int64_t)(k - 1) * ld_q1[f]]; }
+    __device__ __forceinline__ float pe1(int k) const { return pe1_[(int64_t)(k - 1) * ld_pe1]; }
+    __device__ __forceinline__ void emit(int f, int, float v)
+    {
+        *q2_[f] = v;
+        q2_[f] += ld_q2[f];
+    }
+};
 
-// kord <= 7: the level-parallel kernel while one lane per column leaves the chip
-// mostly idle (FV3_MAPPM_PATH=serial|levels overrides, for tests and A/B).
-bool use_levels_kernel(const MappmArgs& a, int64_t max_cols = kLevelsMaxCols)
+// DevColN of column c over the first NF fields of a
+template <int NF>
+__device__ __forceinline__ DevColN<NF> make_cols(const MappmPairArgs& a, int64_t c)
 {
-    const char* p = fv3::variant_env("FV3_MAPPM_PATH");
-    if (p && p[0] == 's') return false;
-    if (a.km > 1000 || a.kn > 1000) return false;
-    if (p && p[0] == 'l') return true;
-    return a.ncol < max_cols;
+    DevColN<NF> d;
+    d.pe1_ = a.pe1 + col_offset(a.l_pe1, c);
+    d.edge.pe2_ = a.pe2 + col_offset(a.l_pe2, c);
+    d.ld_pe1 = a.l_pe1.ld;
+    d.edge.ld_pe2 = a.l_pe2.ld;
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        d.q1_[f] = a.q1[f] + col_offset(a.l_q1[f], c);
+        d.q2_[f] = a.q2[f] + col_offset(a.l_q2[f], c);
+        d.ld_q1[f] = a.l_q1[f].ld;
+        d.ld_q2[f] = a.l_q2[f].ld;
+    }
+    d.edge.kn = a.kn;
+    d.edge.seek(1);
+    return d;
 }
 
-// Pairs of fields: the pair kernel on two or three lanes per column beats the
-// level-parallel kernel (one field per launch) from ~10,000 columns
-// (tools/ab.py, profiles/r05zr_mappm_small_lanes.log and
-// r05zs_mappm_small_lanes.log, two fields, levels / three lanes: 6,912 columns 47 / 59 us,
-// 10,368 63 / 59 us, C48 13,824 77 / 60 us, C96 55,296 252 / 86 us)
-constexpr int64_t kLevelsMaxColsPairs = 10240;
+#ifndef FV3_MAPPM_PAIR_CARRY
+#define FV3_MAPPM_PAIR_CARRY 1  // 0: tools A/B builds
+#endif
+template <bool K1>
+__global__ __launch_bounds__(256) void mappm_ppm_pair_kernel(MappmPairArgs a)
+{
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.ncol) return;
+    DevColN<2> d = make_cols<2>(a, c);
+    mappm_ppm_columns<2, DevColN<2>, FV3_MAPPM_PAIR_CARRY != 0>(d, a.km, a.kn, K1 ? 1 : a.iv, K1 ? 1 : a.kord);
+}
 
-bool launch_split_single(const MappmArgs& a, hipStream_t stream);  // below the split kernels
+// Small grids with one lane per column left the SIMDs short of waves (one rank's share
+// of C384 at world 8, 110,592 columns: 1.7 waves per SIMD, the serial remap's latency
+// unhidden).  Here each column runs on LANES = 2 or 3 lanes: lane p streams the outputs
+// split_bound(p) .. split_bound(p + 1) - 1, the first from input layer 1, each later one
+// from the input layer where the single pass begins its first output (mappm_multi.h,
+// "two lanes per column").  A block is LANES waves over the same 64 columns, wave p the
+// lanes p, so every lane of a wave is in the same phase of its column (neighbouring
+// columns' remap events mostly coincide; with the shares mixed in one wave they diverge
+// at every level).  A later lane finds its start layer in two rounds of loads; every lane
+// checks the sortedness that the start layers rely on on the edges it streams, and after
+// the block barrier the first lane re-runs the single pass on any column the checks did
+// not prove (unsorted or NaN edges).  The host runs this kernel for kn >= LANES only, on
+// NF = 2 fields (fv3_mappm_multi's pairs) or one (fv3_mappm_ex).
+template <int NF, bool K1, int LANES>
+__global__ __launch_bounds__(64 * LANES) void mappm_ppm_pair_split_kernel(MappmPairArgs a)
+{
+    const int iv = K1 ? 1 : a.iv, kord = K1 ? 1 : a.kord;
+    __shared__ SplitCheck s_chk[LANES - 1][64];  // of the lanes after the first
+    __shared__ int s_l0[LANES - 1][64];
+    const int lane = threadIdx.x & 63;
+    const int part = threadIdx.x >> 6;
+    const int64_t c0 = (int64_t)blockIdx.x * 64 + lane;
+    const bool valid = c0 < a.ncol;
+    const int64_t c = valid ? c0 : a.ncol - 1;  // spare lanes only pass the barrier
+    DevColN<NF> d = make_cols<NF>(a, c);
+    const int km = a.km, kn = a.kn;
+    // this lane's outputs [kf, kl] and first input layer (one call site for every lane);
+    // the bounds of each p are scalar arithmetic, selected per wave (as one expression of
+    // `part` they are vector arithmetic: 65,536 columns, one field, 49.9 -> 50.4 us)
+    int kf = 1, kl = kn;
+#pragma unroll
+    for (int p = 0; p < LANES; ++p)
+        if (part == p) {
+            kf = split_bound<LANES>(p, kn);
+            kl = split_bound<LANES>(p + 1, kn) - 1;
+        }
+    const int Lf = part == 0 ? 1 : split_first_layer(d, km, kf);
+    SplitCheck chk{1, km};
+    if (valid) {
+        // the output pointers and the edge cursor where the single pass has them once
+        // output kf - 1 is written
+        float* q2c[NF];
+        for (int f = 0; f < NF; ++f) {
+            q2c[f] = d.q2_[f];
+            d.q2_[f] += (int64_t)(kf - 1) * d.ld_q2[f];
+        }
+        d.edge.seek(kf);
+        mappm_ppm_columns<NF, DevColN<NF>, FV3_MAPPM_PAIR_CARRY != 0, true>(d, km, kn, iv, kord, kf, kl, Lf, &chk);
+        for (int f = 0; f < NF; ++f) d.q2_[f] = q2c[f];
+    }
+    if (part > 0) {
+        s_chk[part - 1][lane] = chk;
+        s_l0[part - 1][lane] = Lf;
+    }
+    __syncthreads();
+    if (part == 0 && valid) {
+        SplitCheck chks[LANES] = {chk};
+        int L0[LANES] = {1};
+        for (int p = 1; p < LANES; ++p) {
+            chks[p] = s_chk[p - 1][lane];
+            L0[p] = s_l0[p - 1][lane];
+        }
+        if (!split_joins<LANES>(chks, L0, km)) {
+            // the fix-up: this column's single pass, over what the lanes wrote
+            d.edge.seek(1);
+            mappm_ppm_columns<NF, DevColN<NF>, FV3_MAPPM_PAIR_CARRY != 0>(d, km, kn, iv, kord);
+        }
+    }
+}
+
+// NF fields on two or three lanes per column: 64 * lanes threads per 64 columns
+template <int NF>
+hipError_t launch_split(MappmPairArgs a, int lanes, hipStream_t stream)
+{
+    const void* kfn = pick_k1(a.iv, a.kord, [&](auto k1) {
+        constexpr bool K1 = decltype(k1)::value;
+        return lanes == 3 ? (const void*)mappm_ppm_pair_split_kernel<NF, K1, 3>
+                          : (const void*)mappm_ppm_pair_split_kernel<NF, K1, 2>;
+    });
+    void* kargs[] = {&a};
+    return hipLaunchKernel(kfn, dim3((unsigned)((a.ncol + 63) / 64)), dim3(64 * lanes), kargs, 0, stream);
+}
 
 int launch_mappm(MappmArgs a, hipStream_t stream)
 {
@@ -561,333 +706,46 @@ int launch_mappm(MappmArgs a, hipStream_t stream)
 #else
         FV3_REQUIRE_CODE(FV3_ERR_UNSUPPORTED, false, "mappm: kord > 7 runs on the exact kernels only");
 #endif
-    } else if (launch_split_single(a, stream)) {
-        // one field on two or three lanes per column
-    } else if (use_levels_kernel(a)) {
+    } else if (const PpmKernel kernel = ppm_kernel(1, a.ncol, a.km, a.kn); kernel == kPpmLevels) {
         const int block = a.km + 1 > 64 ? 128 : 64;
         const size_t lds = sizeof(float) * (9 * (size_t)(a.km + 2) + (size_t)(a.kn + 2));
         FV3_REQUIRE(lds <= 64 * 1024, "mappm: km=%d kn=%d too large for the level-parallel path", a.km, a.kn);
         FV3_REQUIRE(a.ncol <= 0x7fffffff, "mappm: ncol too large for the level-parallel path");
         hipLaunchKernelGGL(mappm_ppm_levels_kernel, dim3((unsigned)a.ncol), dim3(block), lds, stream, a);
-    } else {
+    } else if (kernel == kPpmLanes1) {
         const int block = 256;
         const int64_t grid = (a.ncol + block - 1) / block;
         // q1 / pe1 by buffer loads wherever they fit 32-bit offsets (FV3_MAPPM_PPM_BUF=0:
         // 64-bit addresses, A/B)
         bool buf = fits_c32(a.l_pe1, a.ncol, a.km + 1) && fits_c32(a.l_q1, a.ncol, a.km);
         if (const char* e = fv3::variant_env("FV3_MAPPM_PPM_BUF")) buf = buf && atoi(e) != 0;
-        const bool k1 = is_k1(a.iv, a.kord);
-        const void* kfn = k1 ? (buf ? (const void*)mappm_ppm_kernel<true, true> : (const void*)mappm_ppm_kernel<true, false>)
-                             : (buf ? (const void*)mappm_ppm_kernel<false, true> : (const void*)mappm_ppm_kernel<false, false>);
+        const void* kfn = pick_k1(a.iv, a.kord, [&](auto k1) {
+            constexpr bool K1 = decltype(k1)::value;
+            return buf ? (const void*)mappm_ppm_kernel<K1, true> : (const void*)mappm_ppm_kernel<K1, false>;
+        });
         void* kargs[] = {&a};
         FV3_HIP(hipLaunchKernel(kfn, dim3((unsigned)grid), dim3(block), kargs, 0, stream));
+    } else {  // one field on two or three lanes per column
+        const MappmPairArgs pa{a.pe1, a.pe2, a.l_pe1, a.l_pe2, {a.q1, nullptr}, {a.q2, nullptr}, {a.l_q1, {}},
+                               {a.l_q2, {}}, a.ncol, a.km, a.kn, a.iv, a.kord};
+        FV3_HIP(launch_split<1>(pa, kernel, stream));
     }
     FV3_LAUNCH_CHECK();
     return FV3_OK;
 }
 
-// ---- two fields on one column's edges (fv3_mappm_multi) ----
-
-// DevCol for mappm_ppm_columns<NF> (NF = 1, 2): fields f emit output k in turn, so each
-// keeps its own running output pointer
-template <int NF>
-struct DevColN {
-    const float* pe1_;
-    const float* pe2_;
-    const float* q1_[NF];
-    float* q2_[NF];
-    int64_t ld_pe1, ld_pe2, ld_q1[NF], ld_q2[NF];
-    int kn;
-    const float* pe2_next;
-    float nb;  // as DevCol::nb
-    __device__ __forceinline__ float q1(int f, int k) const { return q1_[f][(int64_t)(k - 1) * ld_q1[f]]; }
-    __device__ __forceinline__ float pe1(int k) const { return pe1_[(int64_t)(k - 1) * ld_pe1]; }
-    __device__ __forceinline__ float pe2(int k) const { return pe2_[(int64_t)(k - 1) * ld_pe2]; }
-    __device__ __forceinline__ void emit(int f, int, float v)
-    {
-        *q2_[f] = v;
-        q2_[f] += ld_q2[f];
-    }
-    __device__ __forceinline__ float next_edge(int k)
-    {
-        if (k + 1 > kn + 1) return 0.0f;
-#if FV3_MAPPM_EDGE_AHEAD
-        const float r = nb;
-        pe2_next += ld_pe2;
-        nb = (k + 2 <= kn + 1) ? *pe2_next : 0.0f;
-#else
-        const float r = *pe2_next;
-        pe2_next += ld_pe2;
-#endif
-        return r;
-    }
-};
-using DevColPair = DevColN<2>;
-
-template <bool K1>
-__global__ __launch_bounds__(256) void mappm_ppm_pair_kernel(MappmPairArgs a)
+// a pair of fields on the streaming kord <= 7 kernels (fv3_mappm_multi), `lanes` per column
+int launch_mappm_pairs(MappmPairArgs a, int lanes, hipStream_t s)
 {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= a.ncol) return;
-    DevColPair d;
-    d.pe1_ = a.pe1 + col_offset(a.l_pe1, c);
-    d.pe2_ = a.pe2 + col_offset(a.l_pe2, c);
-    d.ld_pe1 = a.l_pe1.ld;
-    d.ld_pe2 = a.l_pe2.ld;
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-        d.q1_[f] = a.q1[f] + col_offset(a.l_q1[f], c);
-        d.q2_[f] = a.q2[f] + col_offset(a.l_q2[f], c);
-        d.ld_q1[f] = a.l_q1[f].ld;
-        d.ld_q2[f] = a.l_q2[f].ld;
-    }
-    d.kn = a.kn;
-    d.pe2_next = d.pe2_ + 2 * d.ld_pe2;
-    d.nb = d.kn >= 2 ? *d.pe2_next : 0.0f;
-#ifndef FV3_MAPPM_PAIR_CARRY
-#define FV3_MAPPM_PAIR_CARRY 1  // 0: tools A/B builds
-#endif
-    mappm_ppm_columns<2, DevColPair, FV3_MAPPM_PAIR_CARRY != 0>(d, a.km, a.kn, K1 ? 1 : a.iv, K1 ? 1 : a.kord);
-}
-
-// Small grids with one lane per column left the SIMDs short of waves (one rank's share
-// of C384 at world 8, 110,592 columns: 1.7 waves per SIMD, the serial remap's latency
-// unhidden).  Here each column runs on TWO lanes: the first streams outputs 1 .. kB - 1,
-// the second kB .. kn from the input layer where the single pass begins output kB
-// (mappm_multi.h, "two lanes per column").  A block is two waves over the same 64
-// columns, wave 0 the first halves and wave 1 the second, so every lane of a wave is in
-// the same phase of its column (neighbouring columns' remap events mostly coincide; with
-// the halves mixed in one wave they diverge at every level).  The second lane finds its
-// start layer in two rounds of loads; both lanes check the sortedness that start layer
-// relies on on the edges they stream, and after the block barrier the first lane re-runs
-// the single pass on any column the checks did not prove (unsorted or NaN edges).  The
-// host runs this kernel for kn >= 2 only, on NF = 2 fields (fv3_mappm_multi's pairs) or
-// one (fv3_mappm_ex).
-template <int NF, bool K1>
-__global__ __launch_bounds__(128) void mappm_ppm_pair_split_kernel(MappmPairArgs a)
-{
-    const int iv = K1 ? 1 : a.iv, kord = K1 ? 1 : a.kord;
-    __shared__ int s_ok[64], s_l0[64];
-    const int lane = threadIdx.x & 63;
-    const int part = threadIdx.x >> 6;
-    const int64_t c0 = (int64_t)blockIdx.x * 64 + lane;
-    const bool valid = c0 < a.ncol;
-    const int64_t c = valid ? c0 : a.ncol - 1;  // spare lanes only pass the barrier
-    DevColN<NF> d;
-    d.pe1_ = a.pe1 + col_offset(a.l_pe1, c);
-    d.pe2_ = a.pe2 + col_offset(a.l_pe2, c);
-    d.ld_pe1 = a.l_pe1.ld;
-    d.ld_pe2 = a.l_pe2.ld;
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-        d.q1_[f] = a.q1[f] + col_offset(a.l_q1[f], c);
-        d.q2_[f] = a.q2[f] + col_offset(a.l_q2[f], c);
-        d.ld_q1[f] = a.l_q1[f].ld;
-        d.ld_q2[f] = a.l_q2[f].ld;
-    }
-    d.kn = a.kn;
-    const int km = a.km, kn = a.kn;
-    const int kB = kn / 2 + 1;
-    // this lane's outputs [kf, kl] and first input layer (one call site for every lane)
-    int kf = 1, kl = kB - 1, Lf = 1;
-    if (part == 1) {
-        kf = kB;
-        kl = kn;
-        const float t = d.pe2(kB);
-        Lf = split_first_layer(d, km, t, split_count_sorted(d, km, t));
-    }
-    SplitCheck chk{1, km};
-    if (valid) {
-        // the output pointers and the edge cursor where the single pass has them once
-        // output kf - 1 is written
-        float* q2c[NF];
-        for (int f = 0; f < NF; ++f) {
-            q2c[f] = d.q2_[f];
-            d.q2_[f] += (int64_t)(kf - 1) * d.ld_q2[f];
-        }
-        d.pe2_next = d.pe2_ + (int64_t)(kf + 1) * d.ld_pe2;
-        d.nb = (kf + 2 <= kn + 1) ? *d.pe2_next : 0.0f;
-        mappm_ppm_columns<NF, DevColN<NF>, FV3_MAPPM_PAIR_CARRY != 0, true>(d, km, kn, iv, kord, kf, kl, Lf, &chk);
-        for (int f = 0; f < NF; ++f) d.q2_[f] = q2c[f];
-    }
-    if (part == 1) {
-        s_ok[lane] = chk.mono;
-        s_l0[lane] = Lf;
-    }
-    __syncthreads();
-    if (part == 0 && valid && !split_exact(chk, SplitCheck{s_ok[lane], km}, s_l0[lane], km)) {
-        // the fix-up: this column's single pass, over what the halves wrote
-        d.pe2_next = d.pe2_ + 2 * d.ld_pe2;
-        d.nb = kn >= 2 ? *d.pe2_next : 0.0f;
-        mappm_ppm_columns<NF, DevColN<NF>, FV3_MAPPM_PAIR_CARRY != 0>(d, km, kn, iv, kord);
-    }
-}
-
-// The same on THREE lanes per column (three waves over 64 columns; outputs split at
-// kB1 = kn / 3 + 1 and kB2 = 2 kn / 3 + 1, each later lane starting where the single pass
-// begins its first output): more waves for grids too small to fill the SIMDs even on
-// two.  The host runs it for kn >= 3 only.
-template <int NF, bool K1>
-__global__ __launch_bounds__(192) void mappm_ppm_pair_split3_kernel(MappmPairArgs a)
-{
-    const int iv = K1 ? 1 : a.iv, kord = K1 ? 1 : a.kord;
-    __shared__ int s_ok[2][64], s_l0[2][64], s_exit[64];
-    const int lane = threadIdx.x & 63;
-    const int part = threadIdx.x >> 6;
-    const int64_t c0 = (int64_t)blockIdx.x * 64 + lane;
-    const bool valid = c0 < a.ncol;
-    const int64_t c = valid ? c0 : a.ncol - 1;  // spare lanes only pass the barrier
-    DevColN<NF> d;
-    d.pe1_ = a.pe1 + col_offset(a.l_pe1, c);
-    d.pe2_ = a.pe2 + col_offset(a.l_pe2, c);
-    d.ld_pe1 = a.l_pe1.ld;
-    d.ld_pe2 = a.l_pe2.ld;
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-        d.q1_[f] = a.q1[f] + col_offset(a.l_q1[f], c);
-        d.q2_[f] = a.q2[f] + col_offset(a.l_q2[f], c);
-        d.ld_q1[f] = a.l_q1[f].ld;
-        d.ld_q2[f] = a.l_q2[f].ld;
-    }
-    d.kn = a.kn;
-    const int km = a.km, kn = a.kn;
-    const int kB1 = kn / 3 + 1, kB2 = 2 * kn / 3 + 1;
-    int kf = 1, kl = kB1 - 1, Lf = 1;
-    if (part > 0) {
-        kf = part == 1 ? kB1 : kB2;
-        kl = part == 1 ? kB2 - 1 : kn;
-        const float t = d.pe2(kf);
-        Lf = split_first_layer(d, km, t, split_count_sorted(d, km, t));
-    }
-    SplitCheck chk{1, km};
-    if (valid) {
-        float* q2c[NF];
-        for (int f = 0; f < NF; ++f) {
-            q2c[f] = d.q2_[f];
-            d.q2_[f] += (int64_t)(kf - 1) * d.ld_q2[f];
-        }
-        d.pe2_next = d.pe2_ + (int64_t)(kf + 1) * d.ld_pe2;
-        d.nb = (kf + 2 <= kn + 1) ? *d.pe2_next : 0.0f;
-        mappm_ppm_columns<NF, DevColN<NF>, FV3_MAPPM_PAIR_CARRY != 0, true>(d, km, kn, iv, kord, kf, kl, Lf, &chk);
-        for (int f = 0; f < NF; ++f) d.q2_[f] = q2c[f];
-    }
-    if (part > 0) {
-        s_ok[part - 1][lane] = chk.mono;
-        s_l0[part - 1][lane] = Lf;
-    }
-    if (part == 1) s_exit[lane] = chk.l_exit;
-    __syncthreads();
-    if (part == 0 && valid &&
-        !split3_exact(chk, SplitCheck{s_ok[0][lane], s_exit[lane]}, SplitCheck{s_ok[1][lane], km}, s_l0[0][lane],
-                      s_l0[1][lane], km)) {
-        // the fix-up: this column's single pass, over what the lanes wrote
-        d.pe2_next = d.pe2_ + 2 * d.ld_pe2;
-        d.nb = kn >= 2 ? *d.pe2_next : 0.0f;
-        mappm_ppm_columns<NF, DevColN<NF>, FV3_MAPPM_PAIR_CARRY != 0>(d, km, kn, iv, kord);
-    }
-}
-
-// Where the two-lane kernel pays (tools/ab.py, one box, interleaved; one
-// lane per column vs two).  With whole-column sortedness scans up front
-// (profiles/r05r_mappm_split.log): 65,536 columns 142.7 vs 115.4 us, 110,592 (one rank's
-// C384 band at world 8) 165.7 vs 161.5 us, 147,456 213 vs 228 us, C384 0.78 vs 1.06 ms.
-// With the start layer searched and the checks on the streamed edges
-// (profiles/r05zi_mappm_split.log): 65,536 columns 142.7 vs 99 us, 110,592 165.8 vs
-// 142 us, 147,456 215 vs 215 us, 221,184 262 vs 280 us, C384 0.78 vs 0.93 ms.  Above the
-// level-parallel kernel's range and below kSplitMaxCols columns it runs by default;
-// FV3_MAPPM_SPLIT=0|1 forces it off / on (A/B, tests).
-constexpr int64_t kSplitMaxCols = 147456;
-// Three lanes (profiles/r05zq_mappm_split3.log, one / two / three lanes): 65,536 columns
-// 142.7 / 99 / 86.5 us, 110,592 166 / 141 / 150.5 us, 147,456 214 / 213 / 194 us.  Both
-// split kernels hold 4 waves per SIMD (124-126 VGPRs); three lanes pay while all their
-// waves are resident at once (3 ncol / 64 <= 4 waves x 4 SIMDs x CUs), which 110,592
-// columns exceed.
-constexpr int kSplitWavesPerSimd = 4;
-
-// CUs of the current device, queried once (thread-safe static initialisation)
-int device_cus()
-{
-    static const int n_cu = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-        return n;
-    }();
-    return n_cu;
-}
-
-// lanes per column of the pair kernel: 1, 2 or 3 (FV3_MAPPM_SPLIT=0|1|3 forces one)
-int split_lanes(int64_t ncol, int kn)
-{
-    const int n_cu = device_cus();
-    const char* p = fv3::variant_env("FV3_MAPPM_SPLIT");
-    int n = ncol < kSplitMaxCols ? 2 : 1;
-    if (n == 2 && 3 * ncol <= (int64_t)64 * kSplitWavesPerSimd * 4 * n_cu) n = 3;
-    if (p && p[0] == '0') n = 1;
-    if (p && p[0] == '1') n = 2;
-    if (p && p[0] == '3') n = 3;
-    if (n == 3 && kn < 3) n = 2;
-    if (n == 2 && kn < 2) n = 1;
-    return n;
-}
-
-// One field (fv3_mappm_ex, kord <= 7) on the split kernels (profiles/r05zw_mappm_single_lanes.log,
-// levels / one lane / two / three lanes, us): 13,824 columns 38.6 / 105 / 70 / 49.6,
-// 27,648 67.8 / 108 / 76 / 56.6, C96 55,296 126 / 110 / 81 / 70, 82,944 184 / 127 / 113 /
-// 98, 110,592 242 / 128 / 115 / 119, 147,456 320 / 152 / 139 / 149, 221,184 589 / 190 /
-// 204 / 210.  The one-field split kernels hold 5 waves per SIMD (91 VGPRs): three lanes
-// while all their waves are resident (3 ncol / 64 <= 5 x 4 SIMDs x CUs), then two while
-// theirs are, from 20,480 columns (the level-parallel kernel below).  FV3_MAPPM_SPLIT1=0|2|3
-// forces none / two / three lanes (A/B); a forced FV3_MAPPM_PATH keeps its kernel.
-// Returns false where the host keeps the level-parallel or one-lane kernel.
-constexpr int64_t kSplit1MinCols = 20480;
-constexpr int kSplit1WavesPerSimd = 5;
-
-bool launch_split_single(const MappmArgs& a, hipStream_t stream)
-{
-    if (a.kord > 7 || a.kn < 2) return false;
-    const char* p = variant_env("FV3_MAPPM_SPLIT1");
-    int lanes = 0;
-    if (p) {
-        lanes = atoi(p);
-    } else if (!variant_env("FV3_MAPPM_PATH") && a.ncol >= kSplit1MinCols) {
-        const int64_t resident = (int64_t)64 * kSplit1WavesPerSimd * 4 * device_cus();
-        lanes = 3 * a.ncol <= resident ? 3 : (2 * a.ncol <= resident ? 2 : 0);
-    }
-    if (lanes == 3 && a.kn < 3) lanes = 2;
-    if (lanes != 2 && lanes != 3) return false;
-    MappmPairArgs pa{a.pe1, a.pe2, a.l_pe1, a.l_pe2, {a.q1, nullptr}, {a.q2, nullptr}, {a.l_q1, {}}, {a.l_q2, {}},
-                     a.ncol, a.km, a.kn, a.iv, a.kord};
-    const int64_t grid = (a.ncol + 63) / 64;
-    const bool k1 = is_k1(a.iv, a.kord);
-    if (lanes == 3)
-        hipLaunchKernelGGL((k1 ? mappm_ppm_pair_split3_kernel<1, true> : mappm_ppm_pair_split3_kernel<1, false>),
-                           dim3((unsigned)grid), dim3(192), 0, stream, pa);
-    else
-        hipLaunchKernelGGL((k1 ? mappm_ppm_pair_split_kernel<1, true> : mappm_ppm_pair_split_kernel<1, false>),
-                           dim3((unsigned)grid), dim3(128), 0, stream, pa);
-    return true;
-}
-
-// pairs of fields on the streaming kord <= 7 kernel (fv3_mappm_multi)
-int launch_mappm_pairs(const MappmPairArgs& a, hipStream_t s)
-{
-    const int lanes = split_lanes(a.ncol, a.kn);
-    const bool k1 = is_k1(a.iv, a.kord);
-    if (lanes == 3) {  // three lanes per column: 192 threads per 64 columns
-        const int64_t grid = (a.ncol + 63) / 64;
-        hipLaunchKernelGGL((k1 ? mappm_ppm_pair_split3_kernel<2, true> : mappm_ppm_pair_split3_kernel<2, false>),
-                           dim3((unsigned)grid), dim3(192), 0, s, a);
-    } else if (lanes == 2) {  // two lanes per column: 128 threads per 64 columns
-        const int64_t grid = (a.ncol + 63) / 64;
-        hipLaunchKernelGGL((k1 ? mappm_ppm_pair_split_kernel<2, true> : mappm_ppm_pair_split_kernel<2, false>),
-                           dim3((unsigned)grid), dim3(128), 0, s, a);
+    if (lanes > 1) {
+        FV3_HIP(launch_split<2>(a, lanes, s));
     } else {
         const int block = 256;
         const int64_t grid = (a.ncol + block - 1) / block;
-        hipLaunchKernelGGL((k1 ? mappm_ppm_pair_kernel<true> : mappm_ppm_pair_kernel<false>), dim3((unsigned)grid),
-                           dim3(block), 0, s, a);
+        const void* kfn =
+            pick_k1(a.iv, a.kord, [](auto k1) { return (const void*)mappm_ppm_pair_kernel<decltype(k1)::value>; });
+        void* kargs[] = {&a};
+        FV3_HIP(hipLaunchKernel(kfn, dim3((unsigned)grid), dim3(block), kargs, 0, s));
     }
     FV3_LAUNCH_CHECK();
     return FV3_OK;
@@ -972,15 +830,15 @@ extern "C" int fv3_mappm_multi(const float* pe1, fv3_layout pe1_l, const float* 
     FV3_REQUIRE(ncol / 256 < (int64_t)0x7fffffff, "mappm: ncol too large");
     const hipStream_t s = (hipStream_t)stream;
     int f = 0;
-    // pairs on the streaming kord <= 7 kernel; the level-parallel (small grids) and
+    // pairs on the streaming kord <= 7 kernels; the level-parallel (small grids) and
     // cs_profile (kord > 7) paths, and an odd last field, one field per launch
-    MappmArgs one{pe1, nullptr, pe2, nullptr, pe1_l, {}, pe2_l, {}, ncol, km, kn, iv, kord, nullptr};
-    if (kord <= 7 && !fv3::exact::use_levels_kernel(one, fv3::exact::kLevelsMaxColsPairs)) {
+    const fv3::PpmKernel pair = kord <= 7 ? fv3::ppm_kernel(2, ncol, km, kn) : fv3::kPpmLevels;
+    if (pair != fv3::kPpmLevels) {
         for (; f + 2 <= n_fields; f += 2) {
             fv3::MappmPairArgs a{pe1, pe2, pe1_l, pe2_l, {q1[f], q1[f + 1]}, {q2[f], q2[f + 1]},
                                  {q1_l[f], q1_l[f + 1]}, {q2_l[f], q2_l[f + 1]}, ncol, km, kn, iv, kord};
-            const int st = use_fast(arith, iv, kord) ? fv3::fast::launch_mappm_pairs(a, s)
-                                                     : fv3::exact::launch_mappm_pairs(a, s);
+            const int st = use_fast(arith, iv, kord) ? fv3::fast::launch_mappm_pairs(a, pair, s)
+                                                     : fv3::exact::launch_mappm_pairs(a, pair, s);
             if (st != FV3_OK) return st;
         }
     }

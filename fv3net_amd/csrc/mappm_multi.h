@@ -204,7 +204,10 @@ FV3_HD inline void remap_finish_n(RemapStateN<NF>& s, const ColumnEndsN<NF>& e, 
 // from the top to its last window, the second lane's from its start window to the bottom
 // (a tail it did not stream is read at its exit), and the two ranges must meet; every
 // output edge pair is checked by the lane that consumes it.  A column that fails (or
-// holds NaNs) is run again by the single pass (the kernel's fix-up).
+// holds NaNs) is run again by the single pass (the kernel's fix-up).  Three lanes are the
+// same with two split points (split_bound) and a join of each lane with the next
+// (split_joins); the kernel and the CPU harness (tests/native/mappm_host.cpp) both run
+// the lanes through the functions below.
 struct SplitCheck {
     int mono;    // every pe1 / pe2 pair this lane checked is non-decreasing (NaN: 0)
     int l_exit;  // the input layer after which the lane stopped (km: it ran to the end)
@@ -232,16 +235,37 @@ FV3_HD inline bool split_meets(const SplitCheck& a, int L0, int km)
 {
     return L0 < 4 || L0 > km - 3 || a.l_exit + 7 >= L0;
 }
+// LANES lanes per column: lane p emits outputs split_bound(p) .. split_bound(p + 1) - 1
+// (bounds 1 and kn + 1 at the ends; kn / 2 + 1 for two lanes, kn / 3 + 1 and 2 kn / 3 + 1
+// for three), so every lane has an output when kn >= LANES
+template <int LANES>
+FV3_HD inline int split_bound(int p, int kn)
+{
+    return p * kn / LANES + 1;
+}
+// the join: every lane's checks passed (chk[p], with start layer L0[p]) and each lane's
+// range of checked pe1 pairs meets the next one's; else the column needs the single pass
+template <int LANES>
+FV3_HD inline bool split_joins(const SplitCheck (&chk)[LANES], const int (&L0)[LANES], int km)
+{
+    bool ok = chk[LANES - 1].mono;
+    for (int p = 0; p + 1 < LANES; ++p) ok = ok && chk[p].mono && split_meets(chk[p], L0[p + 1], km);
+    return ok;
+}
+// the join of two and of three lanes by their own names, for callers that hold the lanes'
+// checks as separate values (CPU harnesses written before split_joins)
 FV3_HD inline bool split_exact(const SplitCheck& a, const SplitCheck& b, int L0, int km)
 {
-    return a.mono && b.mono && split_meets(a, L0, km);
+    const SplitCheck chk[2] = {a, b};
+    const int l0[2] = {1, L0};
+    return split_joins<2>(chk, l0, km);
 }
-// three lanes (outputs split at kB1 and kB2; L0b / L0c the second and third lanes'
-// start layers): every lane's checks passed and each lane's range meets the next one's
 FV3_HD inline bool split3_exact(const SplitCheck& a, const SplitCheck& b, const SplitCheck& c, int L0b, int L0c,
                                 int km)
 {
-    return a.mono && b.mono && c.mono && split_meets(a, L0b, km) && split_meets(b, L0c, km);
+    const SplitCheck chk[3] = {a, b, c};
+    const int l0[3] = {1, L0b, L0c};
+    return split_joins<3>(chk, l0, km);
 }
 
 // SPLIT: the remap consumer's view of the column with every output edge it takes checked
@@ -264,12 +288,20 @@ struct EdgeCheckOut {
     }
 };
 
-// the second lane's first input layer from the pe1 count (pe2(kB) outside (pe1(1),
-// pe1(km + 1)): the boundary outputs, emitted from layer 1 on as the single pass does)
+// a later lane's first input layer from the pe1 count, t = pe2(k_first) its first output's
+// top edge (t outside (pe1(1), pe1(km + 1)): the boundary outputs, emitted from layer 1 on
+// as the single pass does)
 template <class Col>
 FV3_HD inline int split_first_layer(Col& c, int km, float t, int cnt)
 {
     return (t <= c.pe1(1) || t >= c.pe1(km + 1)) ? 1 : 1 + cnt;
+}
+// the same for the lane whose first output is k_first > 1, with the count's two rounds of loads
+template <class Col>
+FV3_HD inline int split_first_layer(Col& c, int km, int k_first)
+{
+    const float t = c.pe2(k_first);
+    return split_first_layer(c, km, t, split_count_sorted(c, km, t));
 }
 
 // ---- NF columns on one pressure column, kord <= 7, fully streaming ----

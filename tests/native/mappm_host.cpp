@@ -24,6 +24,7 @@ static inline float fv3_emulated_rcp(float b)
 #define FV3_RCP(b) fv3_emulated_rcp(b)
 #define FV3_HOST_DEVICE_DIV 1
 #endif
+#include "../../fv3net_amd/csrc/mappm_choice.h"
 #include "../../fv3net_amd/csrc/mappm_core.h"
 
 namespace {
@@ -47,6 +48,14 @@ struct Scr {
 
 // whether the default arithmetic serves (iv, kord), as the product's hosts ask it
 extern "C" int host_fast_arith_serves(int iv, int kord) { return fv3::fast_arith_serves(iv, kord) ? 1 : 0; }
+
+// the kord <= 7 kernel the product's host launches (mappm_choice.h): 0 level-parallel, 1 /
+// 2 / 3 lanes per column; the knobs' values as strings, NULL for unset
+extern "C" int host_ppm_kernel_choice(int fields, int64_t ncol, int km, int kn, int n_cu, const char* path,
+                                      const char* split, const char* split1)
+{
+    return fv3::ppm_kernel_choice(fields, ncol, km, kn, n_cu, fv3::PpmKnobs{path, split, split1});
+}
 
 extern "C" int host_mappm(int km, const float* pe1, const float* q1, int kn, const float* pe2,
                           float* q2, int64_t ncol, int iv, int kord)
@@ -206,58 +215,44 @@ extern "C" int host_mappm_multi(int nf, int km, const float* pe1, const float* q
     return -1;
 }
 
-// a column on two lanes (mappm_ppm_columns<NF, .., SPLIT>, the small-grid pair kernel):
-// the two halves one after the other, with the kernel's start-layer search, streamed
-// sortedness checks and single-pass fix-up; kb = 0: the kernel's split point kn / 2 + 1;
-// walk = 1: the second half always from layer 1
-template <int NF>
-static void run_split(int km, const float* pe1, const float* q1, int kn, const float* pe2, float* q2, int64_t ncol,
+// a column on LANES lanes (mappm_ppm_columns<NF, .., SPLIT>, the small-grid split kernel):
+// the lanes one after the other between the kernel's bounds, start layers and join rule
+// (mappm_multi.h), with the single-pass fix-up; kb > 0: the first split point instead of
+// the kernel's; walk = 1: every later lane from layer 1
+template <int NF, int LANES>
+static void run_lanes(int km, const float* pe1, const float* q1, int kn, const float* pe2, float* q2, int64_t ncol,
                       int iv, int kord, int kb, int walk)
 {
     for (int64_t i = 0; i < ncol; ++i) {
         ColN c{pe1, q1, pe2, q2, ncol, i, km, kn};
-        if (kn < 2) {  // the host runs the single-lane kernel
+        if (kn < LANES) {  // the host runs a kernel of fewer lanes
             fv3::mappm_ppm_columns<NF, ColN, true>(c, km, kn, iv, kord);
             continue;
         }
-        const int kB = kb > 0 ? kb : kn / 2 + 1;
-        const float t = c.pe2(kB);
-        const int L0 = walk ? 1 : fv3::split_first_layer(c, km, t, fv3::split_count_sorted(c, km, t));
-        fv3::SplitCheck a{1, km}, b{1, km};
-        fv3::mappm_ppm_columns<NF, ColN, true, true>(c, km, kn, iv, kord, 1, kB - 1, 1, &a);
-        fv3::mappm_ppm_columns<NF, ColN, true, true>(c, km, kn, iv, kord, kB, kn, L0, &b);
-        if (!fv3::split_exact(a, b, L0, km)) fv3::mappm_ppm_columns<NF, ColN, true>(c, km, kn, iv, kord);
+        fv3::SplitCheck chk[LANES];
+        int L0[LANES];
+        for (int p = 0; p < LANES; ++p) {
+            const int kf = (p == 1 && kb > 0) ? kb : fv3::split_bound<LANES>(p, kn);
+            const int kl = (p == 0 && kb > 0) ? kb - 1 : fv3::split_bound<LANES>(p + 1, kn) - 1;
+            L0[p] = (p == 0 || walk) ? 1 : fv3::split_first_layer(c, km, kf);
+            chk[p] = fv3::SplitCheck{1, km};
+            fv3::mappm_ppm_columns<NF, ColN, true, true>(c, km, kn, iv, kord, kf, kl, L0[p], &chk[p]);
+        }
+        if (!fv3::split_joins<LANES>(chk, L0, km)) fv3::mappm_ppm_columns<NF, ColN, true>(c, km, kn, iv, kord);
     }
 }
-// a column on three lanes (the kernel's split points kn / 3 + 1 and 2 kn / 3 + 1, kn >= 3)
-template <int NF>
-static void run_split3(int km, const float* pe1, const float* q1, int kn, const float* pe2, float* q2, int64_t ncol,
-                       int iv, int kord, int walk)
+// the first output of lane p of `lanes` (2 or 3), p = 0 .. lanes
+extern "C" int host_split_bound(int lanes, int p, int kn)
 {
-    for (int64_t i = 0; i < ncol; ++i) {
-        ColN c{pe1, q1, pe2, q2, ncol, i, km, kn};
-        if (kn < 3) {
-            fv3::mappm_ppm_columns<NF, ColN, true>(c, km, kn, iv, kord);
-            continue;
-        }
-        const int kB1 = kn / 3 + 1, kB2 = 2 * kn / 3 + 1;
-        const float t1 = c.pe2(kB1), t2 = c.pe2(kB2);
-        const int L1 = walk ? 1 : fv3::split_first_layer(c, km, t1, fv3::split_count_sorted(c, km, t1));
-        const int L2 = walk ? 1 : fv3::split_first_layer(c, km, t2, fv3::split_count_sorted(c, km, t2));
-        fv3::SplitCheck a{1, km}, b{1, km}, d{1, km};
-        fv3::mappm_ppm_columns<NF, ColN, true, true>(c, km, kn, iv, kord, 1, kB1 - 1, 1, &a);
-        fv3::mappm_ppm_columns<NF, ColN, true, true>(c, km, kn, iv, kord, kB1, kB2 - 1, L1, &b);
-        fv3::mappm_ppm_columns<NF, ColN, true, true>(c, km, kn, iv, kord, kB2, kn, L2, &d);
-        if (!fv3::split3_exact(a, b, d, L1, L2, km)) fv3::mappm_ppm_columns<NF, ColN, true>(c, km, kn, iv, kord);
-    }
+    return lanes == 3 ? fv3::split_bound<3>(p, kn) : fv3::split_bound<2>(p, kn);
 }
 extern "C" int host_mappm_split3(int nf, int km, const float* pe1, const float* q1, int kn, const float* pe2,
                                  float* q2, int64_t ncol, int iv, int kord, int walk)
 {
     if (km < 4 || kn < 1 || kord > 7) return -1;
     switch (nf) {
-        case 1: run_split3<1>(km, pe1, q1, kn, pe2, q2, ncol, iv, kord, walk); return 0;
-        case 2: run_split3<2>(km, pe1, q1, kn, pe2, q2, ncol, iv, kord, walk); return 0;
+        case 1: run_lanes<1, 3>(km, pe1, q1, kn, pe2, q2, ncol, iv, kord, 0, walk); return 0;
+        case 2: run_lanes<2, 3>(km, pe1, q1, kn, pe2, q2, ncol, iv, kord, 0, walk); return 0;
     }
     return -1;
 }
@@ -266,8 +261,8 @@ extern "C" int host_mappm_split(int nf, int km, const float* pe1, const float* q
 {
     if (km < 4 || kn < 1 || kord > 7 || kb > kn || kb == 1) return -1;
     switch (nf) {
-        case 1: run_split<1>(km, pe1, q1, kn, pe2, q2, ncol, iv, kord, kb, walk); return 0;
-        case 2: run_split<2>(km, pe1, q1, kn, pe2, q2, ncol, iv, kord, kb, walk); return 0;
+        case 1: run_lanes<1, 2>(km, pe1, q1, kn, pe2, q2, ncol, iv, kord, kb, walk); return 0;
+        case 2: run_lanes<2, 2>(km, pe1, q1, kn, pe2, q2, ncol, iv, kord, kb, walk); return 0;
     }
     return -1;
 }

@@ -19,12 +19,11 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(params=["split", "split3", "serial", "levels"])
 def path(request, monkeypatch):
     """`split`: pairs of fields on the two-field streaming kernel, each column on two
-    lanes (FV3_MAPPM_SPLIT=1; the default for pairs from ~87,000 to 147,456 columns on 256
-    CUs); `split3`: three lanes per column (FV3_MAPPM_SPLIT=3; the default for pairs from
-    10,240 columns up to ~87,000); `serial`: the same kernel one lane per column
-    (FV3_MAPPM_SPLIT=0, the default above 147,456); `levels`: the small-grid kernel, one
-    field per launch (the default for pairs below 10,240 columns and single fields below
-    20,480).  Single-field calls under a forced FV3_MAPPM_PATH keep that path's kernel."""
+    lanes (FV3_MAPPM_SPLIT=1); `split3`: three lanes per column (FV3_MAPPM_SPLIT=3);
+    `serial`: the same kernel one lane per column (FV3_MAPPM_SPLIT=0); `levels`: the
+    small-grid kernel, one field per launch.  Which of them is the default at which size:
+    ppm_kernel_choice (csrc/mappm_choice.h).  Single-field calls under a forced
+    FV3_MAPPM_PATH keep that path's kernel."""
     set_variant(monkeypatch, "FV3_MAPPM_PATH", "levels" if request.param == "levels" else "serial")
     if request.param != "levels":
         set_variant(monkeypatch, "FV3_MAPPM_SPLIT", {"split": "1", "split3": "3"}.get(request.param, "0"))
@@ -312,3 +311,39 @@ def test_split_defaults_small_level_counts(gpu, km, kn, monkeypatch):
                 assert _bits_equal(a, b), (kord, iv)
             idx = np.sort(rng.choice(ncol, 300, replace=False))
             assert _bits_equal(one_default[:, idx], oracle_mappm(pe1[:, idx], q0[:, idx], pe2[:, idx], iv, kord))
+
+
+@pytest.mark.parametrize("km,kn,ncol", [(4, 2, 65), (5, 4, 63), (7, 5, 129), (12, 7, 64), (9, 8, 200)])
+def test_lane_split_kernel_bounds_and_spare_lanes(gpu, km, kn, ncol, monkeypatch):
+    """The lane-split kernel forced to two and three lanes per column, for one field
+    (FV3_MAPPM_SPLIT1) and a pair (FV3_MAPPM_SPLIT), where its lane bounds and spare lanes
+    can go wrong: few outputs per lane (kn = 2 falls back from three lanes to two), and
+    column counts below, on and above a 64-column block.  Column 0 has decreasing pe2,
+    column 1 a NaN in pe1 and column 2 its bottom pe1 edge out of order, so the fix-up
+    runs.  Every result is bit-identical to the one-lane pair kernel (for one field: on two
+    copies of the field), and to the oracle on the sorted columns."""
+    from tests.remap_exact import mappm_device, mappm_device_multi
+
+    rng = np.random.default_rng(km * 1000 + kn * 10 + ncol)
+    pe1, q0, pe2 = _columns(rng, km, kn, ncol)
+    q1 = _fields(rng, km, ncol, 1)[0]
+    pe2[:, 0] = pe2[::-1, 0]
+    pe1[km // 2, 1] = np.nan
+    pe1[-1, 2] = pe1[1, 2]
+    for iv, kord in ((1, 1), (0, 7)):  # the K1 and the general build of the kernel
+        set_variant(monkeypatch, "FV3_MAPPM_PATH", "serial")  # pairs on the pair kernels at any size
+        monkeypatch.delenv("FV3_MAPPM_SPLIT1", raising=False)
+        set_variant(monkeypatch, "FV3_MAPPM_SPLIT", "0")
+        ref = [o.cpu().numpy() for o in mappm_device_multi(pe1, [q0, q1], pe2, iv, kord)]
+        ref_one = mappm_device_multi(pe1, [q0, q0], pe2, iv, kord)[0].cpu().numpy()
+        with np.errstate(all="ignore"):
+            for q, r in zip((q0, q1), ref):
+                assert _bits_equal(r[:, 3:], oracle_mappm(pe1[:, 3:], q[:, 3:], pe2[:, 3:], iv, kord)), (iv, kord)
+        for lanes in ("1", "3"):
+            set_variant(monkeypatch, "FV3_MAPPM_SPLIT", lanes)
+            for o, r in zip(mappm_device_multi(pe1, [q0, q1], pe2, iv, kord), ref):
+                assert _bits_equal(o.cpu().numpy(), r), (iv, kord, "pair", lanes)
+        for lanes in ("2", "3"):
+            set_variant(monkeypatch, "FV3_MAPPM_SPLIT1", lanes)
+            got = mappm_device(pe1, q0, pe2, iv, kord).cpu().numpy()
+            assert _bits_equal(got, ref_one), (iv, kord, "one field", lanes)

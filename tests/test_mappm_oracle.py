@@ -415,3 +415,68 @@ def test_two_lane_column_split_bit_identical(host_lib, nf, km, kn):
                     assert f3(nf, km, pe1.ctypes.data, q.ctypes.data, kn, pe2.ctypes.data, out.ctypes.data,
                               ncol, iv, kord, walk) == 0
                     assert _bits_equal(out, ref), (kord, iv, "three lanes", walk)
+
+
+# --- which kord <= 7 kernel the host launches (csrc/mappm_choice.h) ---------------
+LEVELS, ONE, TWO, THREE = 0, 1, 2, 3
+# (fields, CUs, ncol, km, kn, (FV3_MAPPM_PATH, FV3_MAPPM_SPLIT, FV3_MAPPM_SPLIT1), kernel); for
+# two fields LEVELS means the level-parallel kernel, one field per launch
+KERNEL_CHOICE = [
+    (1, 256, 20479, 79, 79, (None, None, None), LEVELS),
+    (1, 256, 20480, 79, 79, (None, None, None), THREE),
+    (1, 256, 109226, 79, 79, (None, None, None), THREE),
+    (1, 256, 109227, 79, 79, (None, None, None), TWO),
+    (1, 256, 163840, 79, 79, (None, None, None), TWO),
+    (1, 256, 163841, 79, 79, (None, None, None), ONE),
+    (1, 256, 30000, 79, 2, (None, None, None), TWO),
+    (1, 256, 30000, 79, 1, (None, None, None), LEVELS),
+    (1, 256, 65536, 79, 1, (None, None, None), ONE),
+    (1, 256, 100, 1001, 79, (None, None, None), ONE),
+    (1, 256, 30000, 1001, 79, (None, None, None), THREE),
+    (1, 64, 27306, 79, 79, (None, None, None), THREE),
+    (1, 64, 27307, 79, 79, (None, None, None), TWO),
+    (1, 64, 40960, 79, 79, (None, None, None), TWO),
+    (1, 64, 50000, 79, 79, (None, None, None), LEVELS),
+    (1, 64, 65536, 79, 79, (None, None, None), ONE),
+    (2, 256, 10239, 79, 79, (None, None, None), LEVELS),
+    (2, 256, 10240, 79, 79, (None, None, None), THREE),
+    (2, 256, 87381, 79, 79, (None, None, None), THREE),
+    (2, 256, 87382, 79, 79, (None, None, None), TWO),
+    (2, 256, 147455, 79, 79, (None, None, None), TWO),
+    (2, 256, 147456, 79, 79, (None, None, None), ONE),
+    (2, 256, 30000, 79, 2, (None, None, None), TWO),
+    (2, 256, 30000, 79, 1, (None, None, None), ONE),
+    (1, 256, 30000, 79, 79, ("serial", None, None), ONE),
+    (1, 256, 200000, 79, 79, ("levels", None, None), LEVELS),
+    (1, 256, 100, 79, 2, (None, None, "3"), TWO),
+    (1, 256, 30000, 79, 79, (None, None, "0"), LEVELS),
+    (1, 256, 30000, 79, 79, ("serial", None, "0"), ONE),
+    (2, 256, 30000, 79, 79, (None, "0", None), ONE),
+    (2, 256, 200000, 79, 79, (None, "1", None), TWO),
+    (2, 256, 200000, 79, 2, (None, "3", None), TWO),
+]
+
+
+def test_kernel_choice_thresholds(host_lib):
+    """ppm_kernel_choice, the one function the launches ask, at each threshold's two sides
+    (level-parallel below 20,480 columns for one field and 10,240 for a pair; three lanes
+    per column while 3 ncol lanes are resident at 5 (one field) / 4 (a pair) waves per SIMD,
+    then two, then one), at the kn and km limits, and under each A/B knob."""
+    fn = host_lib.host_ppm_kernel_choice
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p,
+                   ctypes.c_char_p, ctypes.c_char_p]
+    for fields, cus, ncol, km, kn, knobs, want in KERNEL_CHOICE:
+        got = fn(fields, ncol, km, kn, cus, *(k.encode() if k is not None else None for k in knobs))
+        assert got == want, (fields, cus, ncol, km, kn, knobs)
+
+
+def test_split_lane_bounds(host_lib):
+    """The lanes' output ranges: split at kn / 2 + 1 for two lanes, at kn / 3 + 1 and
+    2 kn / 3 + 1 for three, from output 1 to output kn."""
+    fn = host_lib.host_split_bound
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    for kn in range(2, 201):
+        assert [fn(2, p, kn) for p in range(3)] == [1, kn // 2 + 1, kn + 1], kn
+        assert [fn(3, p, kn) for p in range(4)] == [1, kn // 3 + 1, 2 * kn // 3 + 1, kn + 1], kn

@@ -8,11 +8,10 @@ contract; a level whose reference is all zero must come back exactly zero.  Wher
 pass as coverage); where it does not (kord 5; kord 7 with iv 0) the default must be the
 exact result bit for bit.
 
-Kernels are selected by size, as the product build does.  On a 256-CU device the column
-counts 4,096 / 24,576 / 131,072 / 180,224 give, for one field, the level-parallel, the
-three-lane, the two-lane and the one-lane kernel (mappm.hip, launch_split_single), and
-for pairs the level-parallel kernel per field, then three, two and one lane per column
-(split_lanes).  Nothing here depends on which one the device picks.
+Kernels are selected by size, as the product build does: the column counts 4,096 /
+24,576 / 131,072 / 180,224 are one on each side of every threshold of ppm_kernel_choice
+(csrc/mappm_choice.h; pinned on the CPU by tests/test_mappm_oracle.py) on a 256-CU device,
+for one field and for pairs.  Nothing here depends on which kernel the device picks.
 
 Field families: temperature-like 250 + N(0, 10); zero-mean N(0, 10); non-negative with
 30 % exact zeros, max(0, N(0.524e-4, 1e-4)) (the mean puts 30 % of the draws below zero).

@@ -117,7 +117,8 @@ def test_c384_grid_vs_exact(gpu, kord):
 
 def test_pairs_and_split_lanes_vs_single(gpu):
     """Two fields per pass (mappm_device_multi) and the two- and three-lane kernels the
-    host picks by size: within 1e-6 per level of the single-field fast kernel."""
+    host picks by size (ppm_kernel_choice, csrc/mappm_choice.h): within 1e-6 per level of
+    the single-field fast kernel."""
     import torch
 
     from fv3net_amd import workloads as W
